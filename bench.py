@@ -12,6 +12,15 @@ clustered random/tiles216 mix (first half of all ranks' blocks random) dealt
 to the ranks interleaved.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--gen tiles216|random|repetitive|mix|mixc]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what `value` needs and no more: it generates and compresses the batch, warms
+up, times K decompress steps and prints the result line (`ms_per_step` = one timed step's wall
+time). `--dump-outputs DIR` then writes what the last timed step gave its caller as
+DIR/<name>.npy (dump_outputs below; the same arguments give the same inputs in every run).
+`--full` adds every other leg after the timed steps: the batch check (`verified`), the compress
+kernel and the round trip, reference mode, the variants, latency curve, frame workload, N-API
+and single-block rates and the CPU baselines (each with its own switch below).
 
 With --gpus N > 1 and no torch.distributed environment, the script starts N
 rank processes itself (torch.distributed.run, one per GPU, before touching the
@@ -39,13 +48,17 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=4096)
     ap.add_argument("--gen", default="tiles216")
-    ap.add_argument("--compress-steps", type=int, default=2)
-    ap.add_argument("--extra", type=int, default=1, help="also time the random/repetitive/mix variants")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0's) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (the options below pick among them)")
+    ap.add_argument("--compress-steps", type=int, default=2, help="--full: timed compress launches")
+    ap.add_argument("--extra", type=int, default=1, help="--full: also time the random/repetitive/mix variants")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: the CPU baselines")
     ap.add_argument("--cpu-blocks", type=int, default=64, help="4 MiB blocks per CPU thread (pure-JS baseline)")
-    ap.add_argument("--napi", type=int, default=1, help="time the JS drop-in end to end (host buffers)")
+    ap.add_argument("--napi", type=int, default=1, help="--full: time the JS drop-in end to end (host buffers)")
     ap.add_argument("--frame-blocks", type=int, default=2048,
-                    help="4 MiB blocks per rank in the sharded frame workload (configs[3]; 0 = skip)")
+                    help="--full: 4 MiB blocks per rank in the sharded frame workload (configs[3]; 0 = skip)")
     return ap.parse_args()
 
 
@@ -155,6 +168,39 @@ class Batch:
         torch.cuda.synchronize()
         return bool((self.status == 0).all().item()) and bool(torch.equal(h1, h2)) and \
             bool((self.dec_len == BLOCK).all().item())
+
+
+DUMP_SAMPLE = 8 << 20   # decoded bytes kept by --dump-outputs (as float32: 32 MiB)
+
+
+def dump_outputs(torch, lz4mi, batch, stream, path):
+    """--dump-outputs: what the last timed lz4mi_decompress_blocks launch gave its caller, as .npy
+    files under `path`: `status` and `decoded_len` of every block (float32), `decoded` (float32): the
+    decoded bytes, all of them when they are at most DUMP_SAMPLE, else those at DUMP_SAMPLE
+    positions of the output drawn once from a seeded generator (sorted; the same positions in every
+    run), and `decoded_xxh32` (float64): every block's XXH32 over its decoded bytes, so the bytes
+    outside the sample count too. Gathered in slices below 2^31 bytes."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = batch.dec.numel()
+    if total > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(0x5EED).integers(0, total, DUMP_SAMPLE))
+        parts, step = [], 1 << 30
+        for lo in range(0, total, step):
+            p = pos[np.searchsorted(pos, lo):np.searchsorted(pos, lo + step)] - lo
+            parts.append(batch.dec[lo:lo + step][torch.from_numpy(p).cuda()].cpu())
+        dec = torch.cat(parts)
+    else:
+        dec = batch.dec.cpu()
+    h = torch.zeros(batch.n, dtype=torch.int32, device="cuda")
+    lz4mi.xxh32_blocks_dev(batch.dec.data_ptr(), batch.raw_off.data_ptr(), batch.dec_len.data_ptr(), h.data_ptr(),
+                           batch.n, 0, stream)
+    torch.cuda.synchronize()
+    for name, a in (("decoded", dec.numpy().astype(np.float32)),
+                    ("decoded_len", batch.dec_len.cpu().numpy().astype(np.float32)),
+                    ("status", batch.status.cpu().numpy().astype(np.float32)),
+                    ("decoded_xxh32", (h.cpu().numpy().astype(np.int64) & 0xFFFFFFFF).astype(np.float64))):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def reference_mode(torch, lz4mi, batch, stream_obj, gen, seed0, steps=5):
@@ -661,32 +707,40 @@ def main():
     stream = stream_obj.cuda_stream
 
     n = args.blocks
+    full = args.full
+    solo = full and rank == 0 and world == 1     # the legs that run in a single process only
     batch = Batch(torch, lz4mi, n, args.gen, 1 + rank * n, stream, rank, world)
-    # compress (bit-exact encoder) — timed too, it is the other half of the metric
+    # compress (bit-exact encoder): the timed path's input; with --full timed too, it is the other half of the metric
     batch.compress(lz4mi, stream)
     torch.cuda.synchronize()
-    c_wall, c_kern = timed(torch, dist, lambda: batch.compress(lz4mi, stream), args.compress_steps, 0, stream_obj)
+    c_wall = c_kern = None
+    if full:
+        c_wall, c_kern = timed(torch, dist, lambda: batch.compress(lz4mi, stream), args.compress_steps, 0, stream_obj)
     comp_bytes = int(batch.comp_len.sum().item())
     raw_bytes = n * BLOCK
 
     d_wall, d_kern = timed(torch, dist, lambda: batch.decompress(lz4mi, stream), args.steps, args.warmup, stream_obj)
-    ok = batch.verify(torch, lz4mi, stream)
-    ref_mode = reference_mode(torch, lz4mi, batch, stream_obj, args.gen, 1 + rank * n) if rank == 0 else None
-
-    okt = torch.tensor([0 if ok else 1], dtype=torch.int32, device="cuda")
-    if dist is not None:
-        dist.all_reduce(okt, op=dist.ReduceOp.MAX)
-    (d_wall, c_wall), value, per_rank_ms = weak_scaling(torch, dist, (d_wall, c_wall), (d_kern, c_kern), raw_bytes,
-                                                        args.steps, "cuda")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, lz4mi, batch, stream, args.dump_outputs)
+    okt = ref_mode = None
+    if full:
+        ok = batch.verify(torch, lz4mi, stream)
+        ref_mode = reference_mode(torch, lz4mi, batch, stream_obj, args.gen, 1 + rank * n) if rank == 0 else None
+        okt = torch.tensor([0 if ok else 1], dtype=torch.int32, device="cuda")
+        if dist is not None:
+            dist.all_reduce(okt, op=dist.ReduceOp.MAX)
+    walls, value, per_rank_ms = weak_scaling(torch, dist, (d_wall, c_wall) if full else (d_wall,),
+                                             (d_kern, c_kern) if full else (d_kern,), raw_bytes, args.steps, "cuda")
+    d_wall = walls[0]
     ms_per_step = d_wall / args.steps * 1e3
 
-    lat = latency_curve(torch, lz4mi, batch, stream_obj) if args.extra and rank == 0 and world == 1 else None
-    napi = napi_e2e(batch) if args.napi and rank == 0 and world == 1 else None
-    single = single_block(torch, lz4mi, batch) if args.napi and rank == 0 and world == 1 else None
-    c_base = c_cpu_baseline(batch, cpu_threads()) if args.cpu_baseline and rank == 0 and world == 1 else None
+    lat = latency_curve(torch, lz4mi, batch, stream_obj) if args.extra and solo else None
+    napi = napi_e2e(batch) if args.napi and solo else None
+    single = single_block(torch, lz4mi, batch) if args.napi and solo else None
+    c_base = c_cpu_baseline(batch, cpu_threads()) if args.cpu_baseline and solo else None
 
     extra = {}
-    if args.extra and rank == 0 and world == 1:
+    if args.extra and solo:
         del batch.dec
         for g in (["random", "repetitive", "mix", "mixc"] if args.gen == "tiles216" else []):
             nb = n                      # same occupancy as the headline workload
@@ -713,7 +767,7 @@ def main():
         batch.dec = torch.empty(1, dtype=torch.uint8, device="cuda")
 
     frame = None
-    if args.frame_blocks > 0:
+    if full and args.frame_blocks > 0:
         del batch
         torch.cuda.empty_cache()
         try:
@@ -727,7 +781,6 @@ def main():
                 frame["mix_frame"] = {"error": repr(e)[-500:]}
     achieved = (raw_bytes + comp_bytes) / d_kern / 1e9
     traffic, traffic_src = pmc_traffic(lz4mi, n, args.gen)
-    c_traffic, _ = pmc_traffic(lz4mi, n, args.gen, "pmc_traffic_compress.json")
     line = {
         "metric": METRIC,
         "value": round(value, 2),
@@ -745,27 +798,30 @@ def main():
                                f"device-resident (BASELINE.json configs[1])",
                    "blocks_per_gpu": n, "block_bytes": BLOCK, "generator": args.gen,
                    "compression_ratio": round(raw_bytes / comp_bytes, 3), "parallelism": f"blocks sharded x{world}"},
-        "verified": okt.item() == 0,
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
                      "kernel": "lz4mi_decompress_kernel", "kernel_ms": round(d_kern * 1e3, 3),
                      "algorithmic_bytes_per_launch": raw_bytes + comp_bytes},
-        "value_is": "decompress GB/s of uncompressed bytes (the north-star target); compress and the "
-                    "round trip (compress then decompress of the same bytes) are under 'compress' and "
+        "value_is": "decompress GB/s of uncompressed bytes (the north-star target); with --full, compress and "
+                    "the round trip (compress then decompress of the same bytes) are under 'compress' and "
                     "'roundtrip_GBps'",
-        "compress": {"GBps": round(world * raw_bytes / c_wall * args.compress_steps / 1e9, 2),
-                     "kernel": "lz4mi_compress_gts_kernel", "kernel_ms": round(c_kern * 1e3, 3),
-                     "hbm_frac": round((raw_bytes + comp_bytes) / c_kern / 1e9 / HBM_PEAK_GBPS, 4),
-                     "algorithmic_bytes_per_launch": raw_bytes + comp_bytes, "traffic": c_traffic},
-        "roundtrip_GBps": round(world * raw_bytes / (c_wall / args.compress_steps + d_wall / args.steps) / 1e9, 2),
         "build_id": lz4mi.build_id(),
     }
+    if full:
+        c_wall = walls[1]
+        c_traffic, _ = pmc_traffic(lz4mi, n, args.gen, "pmc_traffic_compress.json")
+        line["verified"] = okt.item() == 0
+        line["compress"] = {"GBps": round(world * raw_bytes / c_wall * args.compress_steps / 1e9, 2),
+                            "kernel": "lz4mi_compress_gts_kernel", "kernel_ms": round(c_kern * 1e3, 3),
+                            "hbm_frac": round((raw_bytes + comp_bytes) / c_kern / 1e9 / HBM_PEAK_GBPS, 4),
+                            "algorithmic_bytes_per_launch": raw_bytes + comp_bytes, "traffic": c_traffic}
+        line["roundtrip_GBps"] = round(world * raw_bytes / (c_wall / args.compress_steps + d_wall / args.steps) / 1e9, 2)
     if traffic_src:
         line["roofline"]["traffic_source"] = traffic_src
     if ref_mode is not None:
         line["reference_mode"] = ref_mode
     if world > 1:   # every rank's average launch time: the imbalance the max hides
-        line["per_rank_kernel_ms"] = {"decompress": per_rank_ms[0], "compress": per_rank_ms[1]}
+        line["per_rank_kernel_ms"] = dict(zip(("decompress", "compress"), per_rank_ms))
     if frame is not None:
         line["frame"] = frame
     if extra:
@@ -777,7 +833,7 @@ def main():
     if napi is not None:
         line["napi_end_to_end"] = napi
         line["reference_benchmark"] = reference_benchmark(bool(args.cpu_baseline))
-    if args.cpu_baseline and rank == 0 and world == 1:
+    if args.cpu_baseline and solo:
         line["cpu_baseline"] = js_cpu_baseline(args.gen if args.gen in ("tiles216", "random", "repetitive")
                                                else "tiles216", args.cpu_blocks)
         line["cpu_baseline_c_oracle"] = c_base

@@ -3,7 +3,7 @@
 #   STEPS="tests bench prof pmc" bash tools/gpu_round.sh TAG
 # steps:
 #   tests      the GPU suite (PYTEST_ARGS adds selectors, e.g. "-k small")
-#   bench      the bench line (BENCH_ARGS adds flags)
+#   bench      the whole bench line (bench.py --full; BENCH_ARGS adds flags)
 #   prof       rocprofv3 --kernel-trace --stats of the bench command (headline + compress only)
 #   pmc        FETCH_SIZE / WRITE_SIZE passes of the decode and compress kernels (tools/pmc_traffic.sh)
 #   inst       instruction counters of both kernels on the bench workload (one --pmc pass each)
@@ -24,10 +24,10 @@ for step in $STEPS; do
     rc=$?; echo "pytest rc=$rc"; grep -E "passed|failed|FAILED|Error" $O/pytest.log | tail -12
     [ $rc -eq 0 ] || exit $rc ;;
   bench)
-    timeout -k 10 900 python -u bench.py $BENCH_ARGS > $O/bench.json 2> $O/bench.err || { echo bench failed; tail -20 $O/bench.err; exit 1; }
+    timeout -k 10 900 python -u bench.py --full $BENCH_ARGS > $O/bench.json 2> $O/bench.err || { echo bench failed; tail -20 $O/bench.err; exit 1; }
     echo "bench ok"; tail -c 4000 $O/bench.json ;;
   prof)
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python -u bench.py --steps 5 --warmup 1 --extra 0 --cpu-baseline 0 --napi 0 --frame-blocks 0 > $O/prof_bench.json 2>&1 || { echo rocprof failed; exit 1; }
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python -u bench.py --full --steps 5 --warmup 1 --extra 0 --cpu-baseline 0 --napi 0 --frame-blocks 0 > $O/prof_bench.json 2>&1 || { echo rocprof failed; exit 1; }
     echo "rocprof ok" ;;
   pmc)
     timeout -k 10 900 bash tools/pmc_traffic.sh $O/pmc tiles216 > $O/pmc.log 2>&1 || { echo pmc failed; tail -5 $O/pmc.log; exit 1; }
