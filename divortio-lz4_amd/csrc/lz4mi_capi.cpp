@@ -32,6 +32,8 @@ extern "C" hipError_t lz4mi_launch_decompress_small(const uint8_t*, const uint64
                                                     uint32_t*, int32_t*, uint32_t, uint32_t, uint32_t, void*, int,
                                                     int, hipStream_t);
 extern "C" size_t lz4mi_small_scratch_bytes(uint32_t, uint32_t, uint32_t);
+extern "C" hipError_t lz4mi_launch_sizes(const uint8_t*, const uint64_t*, const uint32_t*, uint32_t*, int32_t*,
+                                         uint32_t, int, hipStream_t);
 extern "C" hipError_t lz4mi_launch_compress(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
                                             const uint64_t*, uint32_t*, uint32_t, int32_t*, hipStream_t);
 extern "C" hipError_t lz4mi_launch_frame_pack(const uint8_t*, const uint64_t*, const uint32_t*, const uint8_t*,
@@ -512,6 +514,46 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
                                                   n + pre, hipMemcpyDeviceToHost, s));
         }
     }
+    LZ4MI_TRY(hipStreamSynchronize(s));
+    return LZ4MI_OK;
+}
+
+int32_t lz4mi_decoded_sizes(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t* out_len,
+                            int32_t* status, uint32_t nblocks, uint32_t flags, void* stream) {
+    if (flags & ~(LZ4MI_DEVICE_PTRS | LZ4MI_FRAME_WORDS)) return LZ4MI_ERR_ARG;
+    if (!out_len || !status || ((!in || !in_off || !in_len) && nblocks)) return LZ4MI_ERR_ARG;
+    DeviceGuard dg;
+    if (dg.status()) return dg.status();
+    if (nblocks == 0) return LZ4MI_OK;
+    const int fw = (flags & LZ4MI_FRAME_WORDS) ? 1 : 0;
+    if (flags & LZ4MI_DEVICE_PTRS) {   // no scratch: nothing to lock
+        LZ4MI_TRY(lz4mi_launch_sizes(in, in_off, in_len, out_len, status, nblocks, fw, pick_stream(stream)));
+        return LZ4MI_OK;
+    }
+    std::lock_guard<std::mutex> lk(g_ctx.mu);
+    hipStream_t s = g_ctx.stream;
+    auto bytes = [&](uint32_t b) -> uint64_t { return (fw && (in_len[b] & 0x80000000u)) ? 0 : in_len[b]; };
+    std::vector<uint64_t> d_in_off(nblocks);
+    uint64_t in_total = 0;
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        d_in_off[b] = in_total;
+        in_total += round16(bytes(b));
+    }
+    LZ4MI_TRY(g_ctx.in.ensure(in_total + 64, s));
+    LZ4MI_TRY(g_ctx.meta.ensure((size_t)nblocks * (8 + 4 + 4 + 4) + 64, s));
+    uint64_t* m_in_off = g_ctx.meta.as<uint64_t>();
+    uint32_t* m_in_len = (uint32_t*)(m_in_off + nblocks);
+    uint32_t* m_out_len = m_in_len + nblocks;
+    int32_t* m_status = (int32_t*)(m_out_len + nblocks);
+    for (uint32_t b = 0; b < nblocks; ++b)
+        if (bytes(b))
+            LZ4MI_TRY(hipMemcpyAsync(g_ctx.in.as<uint8_t>() + d_in_off[b], in + in_off[b], bytes(b),
+                                     hipMemcpyHostToDevice, s));
+    LZ4MI_TRY(hipMemcpyAsync(m_in_off, d_in_off.data(), 8ull * nblocks, hipMemcpyHostToDevice, s));
+    LZ4MI_TRY(hipMemcpyAsync(m_in_len, in_len, 4ull * nblocks, hipMemcpyHostToDevice, s));
+    LZ4MI_TRY(lz4mi_launch_sizes(g_ctx.in.as<uint8_t>(), m_in_off, m_in_len, m_out_len, m_status, nblocks, fw, s));
+    LZ4MI_TRY(hipMemcpyAsync(out_len, m_out_len, 4ull * nblocks, hipMemcpyDeviceToHost, s));
+    LZ4MI_TRY(hipMemcpyAsync(status, m_status, 4ull * nblocks, hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipStreamSynchronize(s));
     return LZ4MI_OK;
 }

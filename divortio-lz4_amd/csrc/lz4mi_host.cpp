@@ -298,3 +298,58 @@ extern "C" int64_t lz4mi_host_decompress_block(const uint8_t* in, uint64_t in_to
     return decompress_block(Arr{in, (int64_t)in_total}, in_off, in_off + in_size, OutArr{out, (int64_t)out_total},
                             out_off, Arr{dict, (int64_t)dict_len}, !(flags & (LZ4MI_JS_COMPAT | LZ4MI_JS_EXACT)));
 }
+
+// ---------------------------------------------------------------------------
+// Decoded size of one block on the calling thread: the sequence walk of decompressBlock
+// (src/block/blockDecompress.js:55-139) with the copies left out, the checker of the GPU
+// size pass (lz4mi_size.hip). Only the two errors that do not depend on output positions
+// exist here: Malformed Input (:75) and Invalid Offset 0 (:128), Malformed tested first
+// within a sequence. Lengths accumulate in 64 bits.
+extern "C" int64_t lz4mi_host_decoded_size(const uint8_t* in, uint64_t in_total, int64_t in_off, int64_t in_size,
+                                           int32_t* status) {
+    if (!status || (!in && in_total) || in_off < 0 || in_size < 0) return LZ4MI_ERR_ARG;
+    const Arr a{in, (int64_t)in_total};
+    int64_t in_pos = in_off;
+    const int64_t in_end = in_off + in_size;
+    uint64_t total = 0;
+    int32_t st = LZ4MI_OK;
+    while (in_pos < in_end) {
+        const uint32_t token = a.at(in_pos++);
+        uint64_t ll = token >> 4;
+        if (ll == 15) {
+            uint32_t s;
+            do {
+                s = a.at(in_pos++);
+                ll += s;
+            } while (s == 255);
+        }
+        if ((uint64_t)in_pos + ll > (uint64_t)in_end) {   // :75
+            st = LZ4MI_ERR_MALFORMED;
+            break;
+        }
+        total += ll;
+        in_pos += (int64_t)ll;
+        if (in_pos >= in_end) break;                      // :123
+        const uint32_t offset = a.at(in_pos) | (a.at(in_pos + 1) << 8);
+        in_pos += 2;
+        if (offset == 0) {                                // :128
+            st = LZ4MI_ERR_OFFSET0;
+            break;
+        }
+        uint64_t ml = token & 15;
+        if (ml == 15) {
+            uint32_t s;
+            do {
+                s = a.at(in_pos++);
+                ml += s;
+            } while (s == 255);
+        }
+        total += ml + 4;
+    }
+    if (total > LZ4MI_MAX_BLOCK) {   // no decode call could be given such a capacity
+        *status = LZ4MI_ERR_OUTPUT_TOO_SMALL;
+        return 0x7FFFFFFF;
+    }
+    *status = st;
+    return (int64_t)total;
+}

@@ -43,7 +43,8 @@ EXPORTS = ("lz4mi_status_message", "lz4mi_init", "lz4mi_device_count", "lz4mi_ve
            "lz4mi_xxh32", "lz4mi_xxh32_blocks", "lz4mi_frame_pack", "lz4mi_generate_blocks",
            "lz4mi_build_id", "lz4mi_xxh32_reset", "lz4mi_xxh32_update", "lz4mi_xxh32_digest",
            "lz4mi_frame_decompress", "lz4mi_frame_index", "lz4mi_compress_chain",
-           "lz4mi_host_compress_block", "lz4mi_host_compress_chain", "lz4mi_host_decompress_block")
+           "lz4mi_host_compress_block", "lz4mi_host_compress_chain", "lz4mi_host_decompress_block",
+           "lz4mi_decoded_sizes", "lz4mi_host_decoded_size")
 
 
 class Lz4miError(RuntimeError):
@@ -110,6 +111,10 @@ def lib():
         L.lz4mi_host_decompress_block.restype = ctypes.c_int64
         L.lz4mi_host_decompress_block.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp,
                                                   ctypes.c_uint64, ctypes.c_int64, _vp, ctypes.c_uint32, ctypes.c_uint32]
+        L.lz4mi_decoded_sizes.restype = ctypes.c_int32
+        L.lz4mi_decoded_sizes.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
+        L.lz4mi_host_decoded_size.restype = ctypes.c_int64
+        L.lz4mi_host_decoded_size.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp]
         L.lz4mi_frame_index.restype = ctypes.c_int32
         L.lz4mi_frame_index.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp]
         L.lz4mi_generate_blocks.restype = ctypes.c_int32
@@ -277,10 +282,58 @@ def _dec_flags(js_compat, js_exact):
     return JS_COMPAT if js_compat else (JS_EXACT if js_exact else 0)
 
 
-def decompress_blocks(blocks, out_sizes, js_compat=False, dictionary=None, js_exact=False):
+def _pack(arrs):
+    n = len(arrs)
+    in_len = np.array([a.size for a in arrs], dtype=np.uint32)
+    in_off = np.zeros(n, dtype=np.uint64)
+    if n > 1:
+        in_off[1:] = np.cumsum(in_len[:-1].astype(np.uint64))
+    src = np.concatenate(arrs) if n and in_len.sum() else np.zeros(1, dtype=np.uint8)
+    return src, in_off, in_len
+
+
+def decoded_sizes(blocks):
+    """Independent compressed blocks -> (statuses, sizes): what each block decodes to, measured
+    on the GPU without decoding (lz4mi_decoded_sizes; statuses 0, ERR_MALFORMED, ERR_OFFSET0, or
+    ERR_OUTPUT_TOO_SMALL above 2^31 - 1 bytes)."""
+    arrs = [_u8(b) for b in blocks]
+    n = len(arrs)
+    src, in_off, in_len = _pack(arrs)
+    sizes = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    if n:
+        _check(lib().lz4mi_decoded_sizes(_p(src), _p(in_off), _p(in_len), _p(sizes), _p(status), n, 0, None))
+    return status, sizes
+
+
+def host_decoded_size(comp, in_off=0, in_size=None):
+    """Decoded size of comp[in_off : in_off + in_size] on the host walker (lz4mi_host_decoded_size,
+    no device needed) -> (status, size)."""
+    a = _u8(comp)
+    if in_size is None:
+        in_size = a.size - in_off
+    st = ctypes.c_int32(0)
+    r = lib().lz4mi_host_decoded_size(_p(a), a.size, in_off, in_size, ctypes.addressof(st))
+    if r < 0:
+        raise Lz4miError(int(r))
+    return int(st.value), int(r)
+
+
+def decompress_blocks(blocks, out_sizes=None, js_compat=False, dictionary=None, js_exact=False):
     """Independent compressed blocks -> (statuses, outputs) (GPU).
+    out_sizes=None: the sizes are measured first (decoded_sizes) and the blocks decoded at them;
+    a block the size pass fails keeps that status and decodes to nothing.
     js_compat: the serial reference-exact kernel; js_exact: the parallel spec
     kernel plus a serial re-decode of the blocks the reference's F1 rewrite changes."""
+    if out_sizes is None:
+        blocks = list(blocks)
+        mst, msz = decoded_sizes(blocks)
+        ok = mst == OK
+        st, outs, out_len = decompress_blocks([b if k else b"" for b, k in zip(blocks, ok)],
+                                              [int(z) if k else 0 for z, k in zip(msz, ok)], js_compat=js_compat,
+                                              dictionary=dictionary, js_exact=js_exact)
+        st = np.where(ok, st, mst).astype(np.int32)
+        return st, outs, out_len
     arrs = [_u8(b) for b in blocks]
     n = len(arrs)
     in_len = np.array([a.size for a in arrs], dtype=np.uint32)
@@ -353,6 +406,13 @@ def decompress_blocks_dev(in_ptr, in_off_ptr, in_len_ptr, out_ptr, out_off_ptr, 
                                          dict_ptr, dict_len, out_len_ptr, status_ptr, nblocks,
                                          DEVICE_PTRS | _dec_flags(js_compat, js_exact) |
                                          (FRAME_WORDS if frame_words else 0), stream or None))
+
+
+def decoded_sizes_dev(in_ptr, in_off_ptr, in_len_ptr, out_len_ptr, status_ptr, nblocks, stream=0, frame_words=False):
+    """Decoded sizes of a batch on device pointers (lz4mi_decoded_sizes): asynchronous on `stream`,
+    nothing read back. frame_words: in_len holds frame size words (bit 31 = stored block)."""
+    _check(lib().lz4mi_decoded_sizes(in_ptr, in_off_ptr, in_len_ptr, out_len_ptr, status_ptr, nblocks,
+                                     DEVICE_PTRS | (FRAME_WORDS if frame_words else 0), stream or None))
 
 
 def compress_blocks_dev(in_ptr, in_off_ptr, in_len_ptr, out_ptr, out_off_ptr, out_len_ptr, nblocks, stream=0):

@@ -814,15 +814,108 @@ def decompress_frame_sharded(frame, verify_checksum=True, group=None, root=0, de
     return got
 
 
-def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=None):
-    """Decode a device-resident frame (1-D uint8 CUDA tensor) on its GPU: the header and the
-    block walk run on the device (lz4mi_frame_decompress), stored blocks are copied and the
-    compressed ones decoded in one batch; the content checksum (FLG 0x04) is verified on the
-    host, streamed piece by piece. Frames the device walk declines (no content size, content
-    size 0, a block layout other than the reference encoder's) are decoded block by block
-    through the host-buffer path, as bufferDecompress.js does. Returns the content as a
-    uint8 CUDA tensor. Raises lz4mi.Lz4miError with the reference's message for the frame's
-    first error."""
+def _verify_content_checksum(frame, pos, out):
+    """The frame's content checksum (at frame[pos:pos + 4]) against out (device), streamed to
+    the host piece by piece (one serial XXH32 chain)."""
+    import lz4mi
+    want = int.from_bytes(frame[pos:pos + 4].cpu().numpy().tobytes(), "little")
+    w = _ChecksumWorker()
+    for p in range(0, out.numel(), CHECKSUM_PIECE):
+        w.feed(out[p:p + CHECKSUM_PIECE].cpu().numpy())
+    if w.digest() != want:
+        raise lz4mi.Lz4miError(lz4mi.ERR_CHECKSUM)
+
+
+def _decode_measured(frame, head, js_exact, s):
+    """The measured route of decompress_frame_device: index the frame's blocks on the device,
+    measure every block's decoded size in one launch (lz4mi_decoded_sizes), lay the output out
+    at the exact positions (exclusive prefix sum on the device) and decode all blocks in one
+    batch. Returns (output, position of the content checksum), or None when the frame has to
+    go to the host path so that its first error and message stay what they were."""
+    import torch
+    import lz4mi
+    dev = frame.device
+    n = frame.numel()
+    bid = (int(head[5]) >> 4) & 7 if head.size > 5 else 7
+    bmax = {4: 65536, 5: 262144, 6: 1048576}.get(bid, 4194304)
+    # the block lists are sized by walking the frame: first for the blocks it would have at a
+    # compression ratio of 4, then, while the walk reports more blocks than listed, 16x as many
+    # (never n / 4 entries up front: every record takes at least its 4-byte size word)
+    most = n // 4 + 2
+    cap = min(most, 4 * (n // bmax) + 64)
+    with torch.cuda.stream(s):
+        while True:
+            pay = torch.empty(cap, dtype=torch.int64, device=dev)
+            word = torch.empty(cap, dtype=torch.int32, device=dev)
+            info = torch.zeros(8, dtype=torch.int64, device=dev)
+            lz4mi.frame_index_dev(frame.data_ptr(), n, pay.data_ptr(), word.data_ptr(), cap, info.data_ptr(),
+                                  s.cuda_stream)
+            h = info.cpu().tolist()
+            if h[0] == 0 and h[7] and h[3] >= cap and cap < most:
+                cap = min(most, cap * 16)
+                continue
+            break
+        nb = int(h[3])
+        if h[0] or h[7] or nb == 0:
+            return None
+        size = int(h[2])
+        if (int(h[1]) & 0x08) and size <= 0:
+            return None
+        pay, word = pay[:nb], word[:nb]
+        sizes = torch.empty(nb, dtype=torch.int32, device=dev)
+        mst = torch.empty(nb, dtype=torch.int32, device=dev)
+        lz4mi.decoded_sizes_dev(frame.data_ptr(), pay.data_ptr(), word.data_ptr(), sizes.data_ptr(), mst.data_ptr(),
+                                nb, s.cuda_stream, frame_words=True)
+        sz64 = sizes.to(torch.int64)
+        ends = torch.cumsum(sz64, 0)
+        comp_max = torch.where(word >= 0, sz64, torch.zeros_like(sz64)).max()   # stored blocks: bit 31 (negative)
+        bad, comp_max, total = torch.stack([(mst != 0).any().to(torch.int64), comp_max, ends[-1]]).cpu().tolist()
+        # the host path reports these frames' errors: a block the walk fails, a compressed block that
+        # decodes to more than the window path's block_max slot, a total other than the content size
+        if bad or (size <= 0 and comp_max > bmax) or (size > 0 and total != size):
+            return None
+        out = torch.empty(max(1, total), dtype=torch.uint8, device=dev)
+        out_off = (ends - sz64).contiguous()
+        out_len = torch.zeros(nb, dtype=torch.int32, device=dev)
+        status = torch.zeros(nb, dtype=torch.int32, device=dev)
+        lz4mi.decompress_blocks_dev(frame.data_ptr(), pay.data_ptr(), word.data_ptr(), out.data_ptr(),
+                                    out_off.data_ptr(), sizes.data_ptr(), out_len.data_ptr(), status.data_ptr(), nb,
+                                    s.cuda_stream, frame_words=True, js_exact=js_exact)
+        st = status.cpu().numpy()
+        if ((st != 0) & (st != lz4mi.ERR_CROSS_BLOCK)).any():
+            return None
+        # blocks that read earlier blocks' output: every block before them is final now; each alone, in order
+        # (the same bytes as the host path's 64 KiB window: a match offset has 16 bits, so it never reaches
+        # further back than the window keeps, and before the frame's first byte both report DICT_OOB)
+        for k in np.nonzero(st == lz4mi.ERR_CROSS_BLOCK)[0].tolist():
+            lz4mi.decompress_blocks_dev(frame.data_ptr(), pay.data_ptr() + 8 * k, word.data_ptr() + 4 * k,
+                                        out.data_ptr(), out_off.data_ptr() + 8 * k, sizes.data_ptr() + 4 * k,
+                                        out_len.data_ptr() + 4 * k, status.data_ptr() + 4 * k, 1, s.cuda_stream,
+                                        frame_words=True, js_exact=js_exact)
+            if int(status[k].cpu()):
+                return None
+        if not bool((out_len == sizes).all()):
+            return None
+    return out[:total], int(h[5])
+
+
+def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=None, report=None):
+    """Decode a device-resident frame (1-D uint8 CUDA tensor) on its GPU. Three routes, in this
+    order; `report` (a dict, optional) receives {"route": "layout" | "measured" | "host"}:
+     - layout: the header and the block walk run on the device (lz4mi_frame_decompress), stored
+       blocks are copied and the compressed ones decoded in one batch at the positions of the
+       reference encoder's layout (content size present, every block but the last fills block_max);
+     - measured: a frame of independent blocks (FLG 0x20) the layout walk declines (no content
+       size, partial blocks): the blocks are indexed on the device, their decoded sizes measured
+       in one launch (lz4mi_decoded_sizes), the output laid out at the exact positions and all
+       blocks decoded in one batch; not taken for js_exact without a content size (the reference
+       decodes such a frame behind a window, where a double-copy-tail rewrite at a block start
+       lands elsewhere than in a contiguous result);
+     - host: everything else (dependent blocks, the empty frame, frames with an error in a
+       block), block by block through the host-buffer path, as bufferDecompress.js does.
+    The content checksum (FLG 0x04) is verified on the host, streamed piece by piece. Returns
+    the content as a uint8 CUDA tensor. Raises lz4mi.Lz4miError with the reference's message
+    for the frame's first error."""
     import torch
     import lz4mi
     # the library binds one device per process: a frame on another device raises ERR_ARG here
@@ -833,25 +926,34 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
         raise lz4mi.Lz4miError(lz4mi.ERR_MAGIC)
     size = int.from_bytes(head[6:14].tobytes(), "little") if head.size >= 14 and head[4] & 0x08 else 0
     out = torch.empty(max(1, size), dtype=torch.uint8, device=frame.device)
+    if report is None:
+        report = {}
     try:
         info = lz4mi.frame_decompress_dev(frame.data_ptr(), frame.numel(), out.data_ptr(), size, s.cuda_stream,
                                           js_exact=js_exact)
     except lz4mi.Lz4miError as e:
         if e.status != lz4mi.ERR_ARG:
             raise
-        host = decompress_frame_host(frame.cpu().numpy(), js_exact=js_exact, verify_checksum=verify_checksum)
-        return torch.from_numpy(host).to(frame.device)
+        del out
+        got = None
+        if head.size > 4 and head[4] & 0x20 and not (js_exact and size == 0):
+            got = _decode_measured(frame, head, js_exact, s)
+        if got is None:
+            report["route"] = "host"
+            host = decompress_frame_host(frame.cpu().numpy(), js_exact=js_exact, verify_checksum=verify_checksum)
+            return torch.from_numpy(host).to(frame.device)
+        report["route"] = "measured"
+        res, pos = got
+        if verify_checksum and head[4] & 0x04:
+            s.synchronize()
+            _verify_content_checksum(frame, pos, res)
+        return res
+    report["route"] = "layout"
     if info["status"]:
         raise lz4mi.Lz4miError(info["status"])
     out = out[:info["written"]]
     if verify_checksum and info["flg"] & 0x04:
-        pos = info["checksum_pos"]
-        want = int.from_bytes(frame[pos:pos + 4].cpu().numpy().tobytes(), "little")
-        w = _ChecksumWorker()
-        for p in range(0, out.numel(), CHECKSUM_PIECE):
-            w.feed(out[p:p + CHECKSUM_PIECE].cpu().numpy())
-        if w.digest() != want:
-            raise lz4mi.Lz4miError(lz4mi.ERR_CHECKSUM)
+        _verify_content_checksum(frame, info["checksum_pos"], out)
     return out
 
 

@@ -117,6 +117,29 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
                                 void* stream);
 
 /*
+ * Batched DECODED SIZES of raw blocks, without decoding them.
+ * Replaces nothing the reference exports: it is the sequence walk of decompressBlock,
+ *           src/block/blockDecompress.js:55-139, with every copy left out, for callers that hold
+ *           blocks without their decoded lengths (frames without a content size or with partial
+ *           blocks, src/buffer/bufferDecompress.js:104-131).
+ * out_len[b] = the sum of the literal and match lengths along block b's token chain, i.e.
+ * outPos - outputOffset where the reference's loop ends or throws; status[b] = the first error, in
+ * sequence order, of the two that do not depend on output positions: LZ4MI_ERR_MALFORMED (:75) and
+ * LZ4MI_ERR_OFFSET0 (:128), Malformed tested first within a sequence. Output Buffer Too Small,
+ * Dictionary Offset Out of Bounds and LZ4MI_ERR_CROSS_BLOCK depend on where the output lies and
+ * are not detected here (the walk goes on). Lengths accumulate in 64 bits: a total above
+ * LZ4MI_MAX_BLOCK gives LZ4MI_ERR_OUTPUT_TOO_SMALL with out_len[b] = 0x7FFFFFFF (no decode call
+ * could be given such a capacity). in_len[b] == 0: size 0, status 0. Bytes past a block's end
+ * read as 0 (the reference's `undefined | 0`): nothing outside in[in_off[b] .. +in_len[b]) is read.
+ * flags: LZ4MI_DEVICE_PTRS (asynchronous on `stream`, no scratch, nothing read back);
+ * LZ4MI_FRAME_WORDS (in_len[b] is a frame size word: bit 31 set = a stored block, size =
+ * word & 0x7FFFFFFF, status 0). Any other flag: LZ4MI_ERR_ARG. One wave per block.
+ */
+int32_t lz4mi_decoded_sizes(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                            uint32_t* out_len, int32_t* status, uint32_t nblocks,
+                            uint32_t flags, void* stream);
+
+/*
  * Batched raw-block COMPRESS (fresh hash table per block: independent blocks).
  * Replaces: compressBlock(src, output, srcStart, srcLen, hashTable, outputOffset)
  *           src/block/blockCompress.js:31-233 (LZ4.compressRaw, src/lz4.js:32) as called by
@@ -250,6 +273,18 @@ int32_t lz4mi_host_compress_chain(const uint8_t* src, uint64_t src_total, int32_
 int64_t lz4mi_host_decompress_block(const uint8_t* in, uint64_t in_total, int64_t in_off, int64_t in_size,
                                     uint8_t* out, uint64_t out_total, int64_t out_off, const uint8_t* dict,
                                     uint32_t dict_len, uint32_t flags);
+/*
+ * Host-CPU decoded size of one block: the walk of lz4mi_decoded_sizes (src/block/blockDecompress.js:55-139
+ * without the copies) on the calling thread, no device needed; the checker of the GPU size pass.
+ * Positions as in lz4mi_host_decompress_block: in[0 .. in_total) is the whole input array, the block is
+ * in[in_off .. +in_size). A length field read past the block's end but inside in_total sees the real
+ * bytes, as in the reference; lz4mi_decoded_sizes has no in_total and reads zeros there (the two agree
+ * when in_total == in_off + in_size). Returns the size (0x7FFFFFFF with *status =
+ * LZ4MI_ERR_OUTPUT_TOO_SMALL above LZ4MI_MAX_BLOCK) and *status = 0 / LZ4MI_ERR_MALFORMED /
+ * LZ4MI_ERR_OFFSET0, or LZ4MI_ERR_ARG (NULL status, negative positions).
+ */
+int64_t lz4mi_host_decoded_size(const uint8_t* in, uint64_t in_total, int64_t in_off,
+                                int64_t in_size, int32_t* status);
 
 /*
  * Block index of a device-resident frame, for decoding its blocks on several devices
