@@ -32,6 +32,12 @@ extern "C" hipError_t lz4mi_launch_decompress_small(const uint8_t*, const uint64
                                                     uint32_t*, int32_t*, uint32_t, uint32_t, uint32_t, void*, int,
                                                     int, hipStream_t);
 extern "C" size_t lz4mi_small_scratch_bytes(uint32_t, uint32_t, uint32_t);
+extern "C" hipError_t lz4mi_launch_decompress_linked(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
+                                                     const uint64_t*, const uint32_t*, const uint8_t*, uint32_t,
+                                                     uint32_t*, int32_t*, uint32_t, uint32_t, uint32_t, void*, int,
+                                                     int, int, hipStream_t);
+extern "C" size_t lz4mi_linked_scratch_bytes(uint32_t, uint32_t, uint32_t);
+extern "C" hipError_t lz4mi_launch_linked_fail(uint32_t*, int32_t*, uint32_t, uint32_t*, hipStream_t);
 extern "C" hipError_t lz4mi_launch_sizes(const uint8_t*, const uint64_t*, const uint32_t*, uint32_t*, int32_t*,
                                          uint32_t, int, hipStream_t);
 extern "C" hipError_t lz4mi_launch_compress(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
@@ -246,6 +252,93 @@ hipError_t decode_launch(const uint8_t* in, const uint64_t* in_off, const uint32
                                    nblocks, mode, ord, s);
 }
 
+// LZ4MI_LINKED (include/lz4mi.h; kernels: lz4mi_expand.hip "linked mode"): the batch is cut into
+// windows in index order on the one stream, each a linked small-path pass whose output is final
+// history for the next. A window holds as many blocks as the scratch cap allows -- compared with
+// what Scratch::ensure really allocates, its slack included --, as the pointer encodings allow
+// (window indices < 2^31; output span + 64 KiB of history < 2^30, so that contiguous slots always
+// fit; with host pointers both spans are checked here and the window cut short, with device pointers
+// the kernel refuses the block), and as LZ4MI_LINKED_WINDOW (test hook, read per call) allows. The
+// crossover LZ4MI_SMALL_BLOCKS does not apply. If not even one block fits, or the allocation
+// fails: one launch per block in order (the batch kernel, nblocks == 1: it reads what precedes the
+// block), then the failure rule over the statuses -- on that last resort a block after the first
+// failure has been written before it is marked, and the export limits are not checked.
+// in_max / out_max: the largest compressed block and capacity if the caller knows them (0: the
+// export limits); h_*: the host's copies of the arrays (nullptr with device pointers).
+uint64_t g_linked_stats[4];   // the last linked call: windows, scratch bytes, x_in_max, x_out_max (lz4mi_debug_linked_stats)
+
+hipError_t linked_launch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
+                         const uint64_t* out_off, const uint32_t* out_cap, const uint8_t* dict, uint32_t dict_len,
+                         uint32_t* out_len, int32_t* status, uint32_t nblocks, int fw, hipStream_t s, Scratch* small,
+                         uint32_t in_max, uint32_t out_max, const uint64_t* h_in_off, const uint32_t* h_in_len,
+                         const uint64_t* h_out_off, const uint32_t* h_out_cap) {
+    constexpr uint32_t kGrain = 64u << 10;
+    const uint32_t xi = in_max ? std::min(kSmallInMax, (in_max + kGrain - 1) / kGrain * kGrain) : kSmallInMax;
+    uint32_t xo = kGrain;
+    while (xo < out_max && xo < kSmallOutMax) xo <<= 1;
+    if (!out_max) xo = kSmallOutMax;
+    auto alloc_of = [&](uint32_t nb) {
+        const size_t need = lz4mi_linked_scratch_bytes(nb, xi, xo);
+        return std::max<size_t>(need + need / 4, 1 << 20);
+    };
+    uint32_t wmax = std::min<uint32_t>(nblocks, ((1u << 30) - 65536u) / xo);
+    const char* we = std::getenv("LZ4MI_LINKED_WINDOW");
+    const uint32_t hook = we ? (uint32_t)std::strtoul(we, nullptr, 10) : 0u;
+    if (hook) wmax = std::min(wmax, hook);
+    uint32_t lo = 0, hi = wmax;
+    while (lo < hi) {   // the most blocks whose allocation stays within the cap
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (alloc_of(mid) <= small_scratch_cap()) lo = mid;
+        else hi = mid - 1;
+    }
+    wmax = lo;
+    if (wmax) {
+        const char* xe = std::getenv("LZ4MI_TEST_SCRATCH_EXTRA_MB");
+        const size_t extra = xe ? (size_t)std::strtoull(xe, nullptr, 10) << 20 : 0;
+        if (small->ensure(lz4mi_linked_scratch_bytes(wmax, xi, xo) + extra, s) != hipSuccess) {
+            (void)hipGetLastError();
+            wmax = 0;
+        }
+    }
+    if (small->ensure(256, s) != hipSuccess) return hipErrorOutOfMemory;
+    hipError_t e = hipMemsetAsync(small->p, 0, 256, s);   // the call's state: no block has failed
+    if (e != hipSuccess) return e;
+    g_linked_stats[0] = 0;
+    g_linked_stats[1] = wmax ? small->cap : 0;
+    g_linked_stats[2] = xi;
+    g_linked_stats[3] = xo;
+    if (!wmax) {
+        for (uint32_t b = 0; b < nblocks; ++b) {
+            e = lz4mi_launch_decompress(in, in_off + b, in_len + b, out, out_off + b, out_cap + b, dict, dict_len,
+                                        out_len + b, status + b, 1, fw ? 4 : 0, nullptr, s);
+            if (e != hipSuccess) return e;
+        }
+        return lz4mi_launch_linked_fail(out_len, status, nblocks, small->as<uint32_t>(), s);
+    }
+    for (uint32_t w0 = 0; w0 < nblocks;) {
+        uint32_t nb = std::min(wmax, nblocks - w0);
+        if (h_out_off) {   // both spans within their 30 bits (one block always is)
+            uint64_t ilo = UINT64_MAX, ihi = 0, olo = UINT64_MAX, ohi = 0;
+            uint32_t k = 0;
+            for (; k < nb; ++k) {
+                ilo = std::min(ilo, h_in_off[w0 + k]);
+                ihi = std::max(ihi, h_in_off[w0 + k] + h_in_len[w0 + k]);
+                olo = std::min(olo, h_out_off[w0 + k]);
+                ohi = std::max(ohi, h_out_off[w0 + k] + h_out_cap[w0 + k]);
+                if (k && (ihi - ilo >= (1u << 30) || ohi - olo + 65536 >= (1u << 30))) break;
+            }
+            nb = k;
+        }
+        e = lz4mi_launch_decompress_linked(in, in_off + w0, in_len + w0, out, out_off + w0, out_cap + w0, dict, dict_len,
+                                           out_len + w0, status + w0, nb, xi, xo, small->p, small_reparse_hook(), fw,
+                                           w0 ? 1 : 0, s);
+        if (e != hipSuccess) return e;
+        ++g_linked_stats[0];
+        w0 += nb;
+    }
+    return hipSuccess;
+}
+
 inline uint64_t round16(uint64_t n) { return (n + 15u) & ~15ull; }
 
 // ---- host XXH32 (reference variant by default, see lz4mi_xxh32.hip) -------
@@ -431,12 +524,19 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
         if (js || !(flags & LZ4MI_DEVICE_PTRS)) return LZ4MI_ERR_ARG;
         mode |= 4;
     }
+    const bool linked = (flags & LZ4MI_LINKED) != 0;
+    if (linked && (flags & (LZ4MI_JS_COMPAT | LZ4MI_JS_EXACT))) return LZ4MI_ERR_ARG;   // (spec mode only: see the header)
     if (nblocks == 0) return LZ4MI_OK;
     if (flags & LZ4MI_DEVICE_PTRS) {
         // the order scratch belongs to the stream: kernels of one stream use it in order
         hipStream_t s = pick_stream(stream);
         StreamCtx* c = stream_ctx(s);
         std::lock_guard<std::mutex> sl(c->mu);
+        if (linked) {
+            LZ4MI_TRY(linked_launch(in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks,
+                                    (mode & 4) ? 1 : 0, s, &c->small, 0, 0, nullptr, nullptr, nullptr, nullptr));
+            return LZ4MI_OK;
+        }
         LZ4MI_TRY(decode_launch(in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks,
                                 mode, s, &c->order, &c->small));
         return LZ4MI_OK;
@@ -444,6 +544,11 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
     if (!in || !out || !in_off || !in_len || !out_off || !out_cap || !out_len || !status) return LZ4MI_ERR_ARG;
     for (uint32_t b = 0; b < nblocks; ++b)
         if (in_len[b] > LZ4MI_MAX_BLOCK || out_cap[b] > LZ4MI_MAX_BLOCK) return LZ4MI_ERR_ARG;
+    if (linked)   // the export limits, and slots ascending and disjoint
+        for (uint32_t b = 0; b < nblocks; ++b)
+            if (in_len[b] > kSmallInMax || out_cap[b] > kSmallOutMax ||
+                (b && out_off[b - 1] + out_cap[b - 1] > out_off[b]))
+                return LZ4MI_ERR_ARG;
     std::lock_guard<std::mutex> lk(g_ctx.mu);
     hipStream_t s = g_ctx.stream;
     // Pack the compressed blocks; stage the output image [lo - hist, hi) so
@@ -484,7 +589,8 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
                                  hipMemcpyHostToDevice, s));
     // js-compat may rewrite bytes anywhere before a match and its result is
     // copied back whole: stage the whole image so untouched bytes survive.
-    const uint64_t up = js ? img : hist;
+    // (linked: a later block may read the caller's bytes in a gap or in the unused tail of a slot)
+    const uint64_t up = (js || linked) ? img : hist;
     if (up) LZ4MI_TRY(hipMemcpyAsync(g_ctx.out.p, out + base, up, hipMemcpyHostToDevice, s));
     if (dlen) LZ4MI_TRY(hipMemcpyAsync(g_ctx.aux.p, dict, dlen, hipMemcpyHostToDevice, s));
     LZ4MI_TRY(hipMemcpyAsync(m_in_off, d_in_off.data(), 8ull * nblocks, hipMemcpyHostToDevice, s));
@@ -493,6 +599,12 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
     LZ4MI_TRY(hipMemcpyAsync(m_out_cap, out_cap, 4ull * nblocks, hipMemcpyHostToDevice, s));
     const uint32_t in_max = *std::max_element(in_len, in_len + nblocks);
     const uint32_t out_max = *std::max_element(out_cap, out_cap + nblocks);
+    if (linked)
+        LZ4MI_TRY(linked_launch(g_ctx.in.as<uint8_t>(), m_in_off, m_in_len, g_ctx.out.as<uint8_t>(), m_out_off, m_out_cap,
+                                dlen ? g_ctx.aux.as<uint8_t>() : nullptr, dlen, m_out_len, m_status, nblocks, 0, s,
+                                &g_ctx.small, std::max(in_max, 1u), std::max(out_max, 1u), d_in_off.data(), in_len,
+                                d_out_off.data(), out_cap));
+    else
     LZ4MI_TRY(decode_launch(g_ctx.in.as<uint8_t>(), m_in_off, m_in_len, g_ctx.out.as<uint8_t>(), m_out_off, m_out_cap,
                             dlen ? g_ctx.aux.as<uint8_t>() : nullptr, dlen, m_out_len, m_status, nblocks, mode, s,
                             &g_ctx.order, &g_ctx.small, std::max(in_max, 1u), std::max(out_max, 1u)));
@@ -516,6 +628,12 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
     }
     LZ4MI_TRY(hipStreamSynchronize(s));
     return LZ4MI_OK;
+}
+
+// The last LZ4MI_LINKED call (tools/bench_linked.py): windows, scratch bytes held, the export sizing.
+int lz4mi_debug_linked_stats(unsigned long long* out) {
+    for (int k = 0; k < 4; ++k) out[k] = g_linked_stats[k];
+    return 0;
 }
 
 int32_t lz4mi_decoded_sizes(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t* out_len,
@@ -763,6 +881,8 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     DeviceGuard dg;
     if (dg.status()) return dg.status();
     if (!(flags & LZ4MI_DEVICE_PTRS) || !info || (flags & LZ4MI_JS_COMPAT)) return LZ4MI_ERR_ARG;
+    const bool linked = (flags & LZ4MI_LINKED) != 0;
+    if (linked && (flags & LZ4MI_JS_EXACT)) return LZ4MI_ERR_ARG;
     for (int k = 0; k < 8; ++k) info[k] = 0;
     hipStream_t s = pick_stream(stream);
     const int mode = (flags & LZ4MI_JS_EXACT) ? 2 : 0;
@@ -821,6 +941,13 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     const uint32_t nc = (uint32_t)hi[3], ns = (uint32_t)hi[4];
     // stored blocks, then every compressed block in one batch (spec or reference-exact)
     LZ4MI_TRY(lz4mi_launch_frame_stored(frame, len, s_in_off, s_len, s_out_off, out, (uint64_t)hi[2], ns, s));
+    // (LZ4MI_LINKED: after the stored copies, the compressed blocks in one linked call -- their slots ascend in
+    // frame order, the stored blocks lie in the gaps; sized for the frame's block_max, which a compressed
+    // block of the reference's layout does not exceed: one that does is refused and decoded alone below)
+    if (nc && linked)
+        LZ4MI_TRY(linked_launch(frame, c_in_off, c_in_len, out, c_out_off, c_out_cap, nullptr, 0, d_out_len, d_status, nc,
+                                0, s, &c->small, (uint32_t)bmax, (uint32_t)bmax, nullptr, nullptr, nullptr, nullptr));
+    else
     if (nc) LZ4MI_TRY(decode_launch(frame, c_in_off, c_in_len, out, c_out_off, c_out_cap, nullptr, 0, d_out_len,
                                     d_status, nc, mode, s, &c->order));
     std::vector<uint32_t> olen(nc), cap(nc), cidx(nc), slen(ns), sidx(ns);
@@ -840,9 +967,10 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     }
     LZ4MI_TRY(hipStreamSynchronize(s));
     // blocks that read earlier blocks' output (dependent frames, or an F1 rewrite at a block start):
-    // every block before them is final now; decode each alone, in order
+    // every block before them is final now; decode each alone, in order (LZ4MI_LINKED: nothing to do
+    // unless a block failed or was refused -- the blocks from there on are resumed here)
     for (uint32_t k = 0; k < nc; ++k) {
-        if (stat[k] != LZ4MI_ERR_CROSS_BLOCK) continue;
+        if (stat[k] != LZ4MI_ERR_CROSS_BLOCK && !(linked && stat[k] == LZ4MI_ERR_ARG)) continue;
         LZ4MI_TRY(decode_launch(frame, c_in_off + k, c_in_len + k, out, c_out_off + k, c_out_cap + k, nullptr, 0,
                                 d_out_len + k, d_status + k, 1, mode, s, nullptr));
         LZ4MI_TRY(hipMemcpyAsync(&olen[k], d_out_len + k, 4, hipMemcpyDeviceToHost, s));

@@ -1131,7 +1131,10 @@ __device__ void f1_fixup(const Ctx c, const DecShared& S, int lane, uint32_t nse
     }
 }
 
-template <bool XP>
+// LK (with XP): a linked window (LZ4MI_LINKED, lz4mi_expand.hip): every block left exported by
+// lz4mi_linked_prep_kernel is within the export limits and is parsed for export whatever its ratio --
+// a one-wave decode would write `out` and read predecessors the gather has not written yet.
+template <bool XP, bool LK = false>
 __device__ __forceinline__ void decompress_block(const DecArgs& a) {
     __shared__ DecShared S;
     const int lane = threadIdx.x;
@@ -1139,6 +1142,7 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
     if (blockIdx.x >= a.nblocks * nseg) return;
     const uint32_t wblk = XP ? blockIdx.x / nseg : blockIdx.x;   // (XP: block-major, segments of a block on
     const uint32_t sg = XP ? blockIdx.x - wblk * nseg : 0u;       //  consecutive CUs, every XCD)
+    if (LK && uniform(a.xcnt[wblk]) == kNotExported) return;     // stored, refused or after a failure: not parsed
     const uint32_t b = a.order ? uniform(a.order[wblk]) : wblk;
     if (!XP && a.redo && !uniform(a.redo[b])) return;   // (small batches, reference mode: the blocks to redo)
 #if LZ4MI_TIMELINE
@@ -1183,9 +1187,9 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
     // (a block of long runs -- output over 32x its compressed size: repetitive data, one periodic
     // match -- decodes faster in one wave, as in the batch kernel: 1.1 ms for 4 MiB at any batch
     // size, against 0.77 ms alone / 1.57 ms for 16 through the pointers, profiles/r06c)
-    const bool xp = XP && (uint32_t)c.in_len <= a.x_in_max && out_cap <= a.x_out_max &&
-                    (uint64_t)out_cap < (uint64_t)c.in_len * kXRatioMax &&
-                    !(a.x_flat1 && (uint64_t)c.in_len * 16 >= (uint64_t)out_cap * 15);
+    const bool xp = XP && (LK || ((uint32_t)c.in_len <= a.x_in_max && out_cap <= a.x_out_max &&
+                                  (uint64_t)out_cap < (uint64_t)c.in_len * kXRatioMax &&
+                                  !(a.x_flat1 && (uint64_t)c.in_len * 16 >= (uint64_t)out_cap * 15)));
     // past the export limits (or ratio >= 32): one wave decodes the block as usual -- segment
     // b mod 256, i.e. workgroup 257 b (mod 256 CUs: a CU of its own for every block, where
     // segment 0 would put the blocks of a batch on one CU)
@@ -1913,6 +1917,8 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
 __global__ __launch_bounds__(64, 4) void lz4mi_decompress_kernel(DecArgs a) { decompress_block<false>(a); }
 // small batches: a wave per segment of each block, sequences exported (lz4mi_expand.hip)
 __global__ __launch_bounds__(64, 4) void lz4mi_decompress_x_kernel(DecArgs a) { decompress_block<true>(a); }
+// a linked window: every parsed block exported (no one-wave shortcuts)
+__global__ __launch_bounds__(64, 4) void lz4mi_decompress_xl_kernel(DecArgs a) { decompress_block<true, true>(a); }
 
 // After phase 0 and after phase 2 of an exported small batch, per block: the segments in order
 // from segment 0 (whose entry is the block's first token): each whose speculative entry equals
@@ -2217,4 +2223,72 @@ extern "C" hipError_t lz4mi_launch_decompress_small(const uint8_t* in, const uin
     r.redo = redo;
     hipLaunchKernelGGL(lz4mi::lz4mi_decompress_kernel, dim3(nblocks), dim3(64), 0, stream, r);
     return hipGetLastError();
+}
+
+// A linked window (LZ4MI_LINKED): the small path with every block exported and the pointers
+// resolved across the window's blocks (lz4mi_expand.hip, "linked mode"). `xs`: scratch of
+// lz4mi_linked_scratch_bytes; its first 256 bytes hold the call's state (zeroed by the caller
+// before the first window: a failure in one window fails the blocks of the later ones).
+// has_prev: the arrays hold an earlier block of the same call before this window's first.
+extern "C" hipError_t lz4mi_launch_linked_prep(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
+                                               const uint64_t*, const uint32_t*, uint32_t*, int32_t*, uint32_t, uint32_t,
+                                               uint32_t, int, int, uint32_t*, uint32_t*, hipStream_t);
+extern "C" hipError_t lz4mi_launch_expand_linked(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
+                                                 const uint64_t*, const uint32_t*, const uint8_t*, uint32_t, uint32_t*,
+                                                 int32_t*, const uint4*, const uint32_t*, lz4mi::SegRec*, uint32_t,
+                                                 uint32_t, uint32_t*, uint32_t, uint32_t*, uint32_t*, int, uint32_t,
+                                                 hipStream_t);
+static size_t linked_head_bytes(uint32_t nblocks) { return (256 + (size_t)nblocks * 8 + 255) / 256 * 256; }
+extern "C" size_t lz4mi_linked_scratch_bytes(uint32_t nblocks, uint32_t x_in_max, uint32_t x_out_max) {
+    return linked_head_bytes(nblocks) + lz4mi_small_scratch_bytes(nblocks, x_in_max, x_out_max);
+}
+extern "C" hipError_t lz4mi_launch_decompress_linked(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                                     uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                                     const uint8_t* dict, uint32_t dict_len, uint32_t* out_len,
+                                                     int32_t* status, uint32_t nblocks, uint32_t x_in_max,
+                                                     uint32_t x_out_max, void* xs, int force_reparse, int frame_words,
+                                                     int has_prev, hipStream_t stream) {
+    using lz4mi::SegRec;
+    if (nblocks == 0) return hipSuccess;
+    const uint32_t stride = lz4mi::seg_block_capacity(x_in_max);
+    uint32_t* xl = (uint32_t*)xs;
+    uint8_t* p = (uint8_t*)xs + linked_head_bytes(nblocks);
+    uint4* xseq = (uint4*)p;
+    p += ((size_t)nblocks * stride * 16 + 255) / 256 * 256;
+    uint32_t* xcnt = (uint32_t*)p;
+    uint32_t* xfirst = xcnt + nblocks;
+    SegRec* xrec = (SegRec*)(xfirst + nblocks);
+    hipError_t e = hipMemsetAsync(p, 0, small_meta_bytes(nblocks), stream);
+    if (e != hipSuccess) return e;
+    p += small_meta_bytes(nblocks);
+    uint32_t* ptr = (uint32_t*)p;
+    p += (size_t)nblocks * x_out_max * 4;
+    uint32_t* aux = (uint32_t*)p;
+    e = lz4mi_launch_linked_prep(in, in_off, in_len, out, out_off, out_cap, out_len, status, nblocks, x_in_max, x_out_max,
+                                 frame_words, has_prev, xl, xcnt, stream);
+    if (e != hipSuccess) return e;
+    // the parse reads the lengths the prep wrote (no stored bit; a block that is not parsed is skipped)
+    lz4mi::DecArgs a{in, in_off, xl + 8, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks, 0, 0};
+    a.xseq = xseq;
+    a.xcnt = xcnt;
+    a.xrec = xrec;
+    a.xseq_stride = stride;
+    a.xsegs = kSegMax;
+    a.x_in_max = x_in_max;
+    a.x_out_max = x_out_max;
+    a.xfirst = xfirst;
+    a.xfirst_w = xfirst;
+    a.xforce = force_reparse;
+    const dim3 grid(nblocks * kSegMax);
+    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_xl_kernel, grid, dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(lz4mi::lz4mi_xverify_kernel, dim3(nblocks), dim3(64), 0, stream, a);
+    a.xphase = 2;
+    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_xl_kernel, grid, dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(lz4mi::lz4mi_xverify_kernel, dim3(nblocks), dim3(64), 0, stream, a);
+    a.xphase = 1;
+    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_xl_kernel, grid, dim3(64), 0, stream, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return lz4mi_launch_expand_linked(in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, xseq,
+                                      xcnt, xrec, kSegMax, stride, ptr, x_out_max, aux, xl, frame_words, nblocks, stream);
 }

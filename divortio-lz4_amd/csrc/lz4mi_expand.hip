@@ -68,6 +68,9 @@ struct ExpArgs {
     uint32_t* best;           // per block: min over failing sequences of (index << 3 | check)
     uint32_t ntiles;          // nblocks * x_out_max / kTile
     uint32_t tshift;          // log2(x_out_max / kTile)
+    // linked mode (LZ4MI_LINKED, below): pointers name positions of the window, not of the block
+    const uint32_t* lbase;    // per block: in_off[b] - win[0]
+    const uint64_t* win;      // win[0]: the window's lowest in_off, win[1]: its lowest out_off
 };
 
 // The output kernels loop over (block, tile) pairs, a tile = kXThreads * kXBytes output bytes,
@@ -164,6 +167,7 @@ __global__ __launch_bounds__(64) void lz4mi_xbase_kernel(ExpArgs a) {
         a.out_len[b] = tb;
     }
     (void)fe;
+    (void)em;
 }
 
 // Per (segment, block): the reference's checks that need absolute output positions (1 capacity,
@@ -208,13 +212,39 @@ __global__ __launch_bounds__(64) void lz4mi_xstatus_kernel(ExpArgs a) {
     }
 }
 
-__global__ __launch_bounds__(kXThreads) void lz4mi_expand_kernel(ExpArgs a) {
+// Linked mode: the source of a match byte below its block's start, y < 0 relative to block b. The
+// walk goes back over the earlier slots (ascending and disjoint: lz4mi_linked_prep_kernel refuses
+// anything else) to the one at or below the position -- a back-reference spans < 64 KiB, so usually
+// one step. Inside the decoded part of an exported block p < b of this window: unresolved, the index
+// of p's pointer for that byte -- strictly below every index of block b, and an entry the expand
+// writes in this call (p is exported, status 0, the byte below its output length). Everything else
+// is final before the gather runs: a gap, a stored block (copied before the gather), the unused tail
+// of a short block, the bytes before the window, the dictionary below out[0]: resolved, relative to
+// the window's lowest out_off (+ 65536: >= 1, the position is less than 64 KiB below block b).
+__device__ __forceinline__ uint32_t link_src(const ExpArgs& a, uint32_t b, int32_t y) {
+    const int64_t pos = (int64_t)a.out_off[b] + y;
+    for (uint32_t p = b; p-- > 0;) {
+        const int64_t po = (int64_t)a.out_off[p];
+        if (pos < po) continue;
+        if (a.xcnt[p] != kNotExported && a.status[p] == 0 && pos - po < (int64_t)min(a.out_len[p], a.out_cap[p]))
+            return p * a.x_out_max + (uint32_t)(pos - po);
+        break;
+    }
+    return kHist | (uint32_t)(pos - (int64_t)a.win[1] + 65536);
+}
+
+// LK: the linked instantiation (lz4mi_expand_linked_kernel, at the end of this file); the unlinked
+// one compiles to what it was.
+template <bool LK>
+__device__ __forceinline__ void expand_body(const ExpArgs& a) {
   bool unres = false;
   X_TILES(a) {
     uint32_t x0 = 0;
     const uint32_t b = X_B(a);
     const uint32_t n = x_span(a, b, X_T(a), x0);
     if (n) {
+        const uint32_t lb = LK ? a.lbase[b] : 0u;          // literal positions: relative to the window's compressed bytes
+        const uint32_t wb = LK ? b * a.x_out_max : 0u;     // output positions: indices of the window's pointer array
         const SegRec* R = a.xrec + (size_t)b * a.nseg;
         const SegGeom G = seg_geom(a.in_len[b]);
         // the segment holding x0 (the first whose end is past it), then its last sequence
@@ -256,12 +286,17 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_expand_kernel(ExpArgs a) {
                 if (x >= q3.x) e = q3;
                 if (x >= q4.x) e = q4;
                 if (x - e.x < e.z) {
-                    v[t] = kLit | (e.y + (x - e.x));
+                    v[t] = kLit | (lb + e.y + (x - e.x));
                 } else {
                     const uint32_t ms = base + e.x + e.z, xa = x + base, d = xa - ms;
                     const int32_t y = (int32_t)(d < e.w ? xa : ms + d % e.w) - (int32_t)e.w;
-                    v[t] = y >= 0 ? (uint32_t)y : (kHist | (uint32_t)(y + 65536));
-                    unres |= y >= 0;
+                    if (LK) {
+                        v[t] = y >= 0 ? wb + (uint32_t)y : link_src(a, b, y);
+                        unres |= v[t] < kUnres;
+                    } else {
+                        v[t] = y >= 0 ? (uint32_t)y : (kHist | (uint32_t)(y + 65536));
+                        unres |= y >= 0;
+                    }
                 }
             }
             uint4* P = (uint4*)(a.ptr + (size_t)b * a.x_out_max + x0);
@@ -295,15 +330,20 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_expand_kernel(ExpArgs a) {
             }
             const uint32_t ex = base + e.x;
             if (x - ex < e.z) {
-                v[t] = kLit | (e.y + (x - ex));
+                v[t] = kLit | (lb + e.y + (x - ex));
             } else {
                 // an overlapping match repeats its first `offset` bytes: point into the period
                 // before the match start, so every pointer lands in an earlier sequence (a chain
                 // hops at most once per sequence, not once per period)
                 const uint32_t ms = ex + e.z, d = x - ms;
                 const int32_t y = (int32_t)(d < e.w ? x : ms + d % e.w) - (int32_t)e.w;
-                v[t] = y >= 0 ? (uint32_t)y : (kHist | (uint32_t)(y + 65536));
-                unres |= y >= 0;
+                if (LK) {
+                    v[t] = y >= 0 ? wb + (uint32_t)y : link_src(a, b, y);
+                    unres |= v[t] < kUnres;
+                } else {
+                    v[t] = y >= 0 ? (uint32_t)y : (kHist | (uint32_t)(y + 65536));
+                    unres |= y >= 0;
+                }
             }
         }
         uint4* P = (uint4*)(a.ptr + (size_t)b * a.x_out_max + x0);
@@ -314,6 +354,7 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_expand_kernel(ExpArgs a) {
     const uint64_t um = __ballot(unres);
     if (um && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(um)) a.flags[0] = 1u;
 }
+__global__ __launch_bounds__(kXThreads) void lz4mi_expand_kernel(ExpArgs a) { expand_body<false>(a); }
 
 // The jump rounds and the chase work on a wave's KiB of output strided: lane l holds bytes
 // l, l + 64, ... l + 960, so each load, gather and store instruction of the wave covers 256
@@ -327,7 +368,8 @@ __device__ __forceinline__ uint32_t x_wave(const ExpArgs& a, uint32_t b, uint32_
     return wbase < n ? n : 0u;
 }
 
-__global__ __launch_bounds__(kXThreads) void lz4mi_jump_kernel(ExpArgs a, int r) {
+template <bool LK>
+__device__ __forceinline__ void jump_body(const ExpArgs& a, int r) {
   if (a.flags[r] == 0) return;
   bool still = false;
   X_TILES(a) {
@@ -340,7 +382,7 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_jump_kernel(ExpArgs a, int r)
     bool mine = false;
     if (*dn == 0) {
         uint32_t* P = a.ptr + (size_t)b * a.x_out_max + wbase + lane;
-        const uint32_t* Q = a.ptr + (size_t)b * a.x_out_max;
+        const uint32_t* Q = LK ? a.ptr : a.ptr + (size_t)b * a.x_out_max;   // (linked: window indices)
         uint32_t v[kXBytes];
 #pragma unroll
         for (int k = 0; k < kXBytes; ++k) v[k] = wbase + lane + 64 * k < n ? P[64 * k] : kLit;
@@ -361,6 +403,7 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_jump_kernel(ExpArgs a, int r)
     const uint64_t sm = __ballot(still);
     if (sm && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(sm)) a.flags[r + 1] = 1u;
 }
+__global__ __launch_bounds__(kXThreads) void lz4mi_jump_kernel(ExpArgs a, int r) { jump_body<false>(a, r); }
 
 // After the jump rounds: every pointer still unresolved is followed to its end (chains the two
 // rounds did not finish: at 64 blocks 0.44 ms of a tiles216 decode, 3.1 ms of a text one).
@@ -432,16 +475,19 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_xf1ptr_kernel(ExpArgs a, int 
     if (__syncthreads_or(any) && threadIdx.x == 0) a.flags[0] = 1u;
 }
 
-__global__ __launch_bounds__(kXThreads) void lz4mi_gather_kernel(ExpArgs a) {
+template <bool LK>
+__device__ __forceinline__ void gather_body(const ExpArgs& a) {
   X_TILES(a) {
     uint32_t x0;
     const uint32_t b = X_B(a);
     const uint32_t n = x_span(a, b, X_T(a), x0);
     if (!n) continue;
     const uint32_t* P = a.ptr + (size_t)b * a.x_out_max + x0;
-    const uint8_t* src = a.in + a.in_off[b];
+    // (linked: resolved pointers are relative to the window's lowest in_off / out_off, whatever block holds them)
+    const uint8_t* src = a.in + (LK ? a.win[0] : a.in_off[b]);
     uint8_t* dst = a.out + a.out_off[b];
-    const int64_t out_off = (int64_t)a.out_off[b];
+    const int64_t out_off = (int64_t)(LK ? a.win[1] : a.out_off[b]);
+    const uint8_t* hist = LK ? a.out + a.win[1] : dst;
     uint4 w[kXBytes / 4];
 #pragma unroll
     for (int q = 0; q < kXBytes / 4; ++q) w[q] = ((const uint4*)P)[q];
@@ -463,7 +509,7 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_gather_kernel(ExpArgs a) {
         uint32_t c = 0;
         if ((v[t] & kHist) == kHist) {            // before the block: the caller's bytes or the dictionary
             const int64_t y = (int64_t)(v[t] & 0x3FFFFFFFu) - 65536;
-            c = out_off + y >= 0 ? dst[y] : (a.dict ? a.dict[(int64_t)a.dict_len + out_off + y] : 0u);
+            c = out_off + y >= 0 ? hist[y] : (a.dict ? a.dict[(int64_t)a.dict_len + out_off + y] : 0u);
         } else if (v[t] & kLit) {
             c = src[v[t] & 0x3FFFFFFFu];
         }
@@ -473,6 +519,167 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_gather_kernel(ExpArgs a) {
         *(uint4*)(dst + x0) = make_uint4(o[0], o[1], o[2], o[3]);
     } else {
         for (uint32_t t = 0; x0 + t < n; ++t) dst[x0 + t] = (uint8_t)(o[t >> 2] >> (8 * (t & 3)));
+    }
+  }
+}
+__global__ __launch_bounds__(kXThreads) void lz4mi_gather_kernel(ExpArgs a) { gather_body<false>(a); }
+
+// ---- linked mode (LZ4MI_LINKED): dependent blocks in one batch -------------------------------
+// A block may reference the 64 KiB of output before it, i.e. the blocks before it. LZ4 control
+// flow never depends on output bytes, so the parse, the sizes and the checks stay per block; only
+// the pointers see across blocks. A window = the blocks of one pass (all pointer arrays in
+// scratch at once). Encoding: an unresolved pointer is an index of the window's pointer array,
+// b * x_out_max + x (< 2^31: at most 512 blocks of 4 MiB); kLit | p: byte p of the compressed
+// bytes counted from the window's lowest in_off; kHist | (q + 65536): output byte q counted from
+// the window's lowest out_off (q < 0: the caller's bytes before the window, or the dictionary
+// below out[0]); both spans fit 30 bits or the block is refused (lz4mi_linked_prep_kernel).
+//
+// Termination of the chase: (1) every hop lands at a strictly lower window index -- inside a block
+// x - offset < x (the periodic form too: it lands in the period before the match), across blocks
+// link_src returns an index of a block p < b; (2) a hop never lands on an entry not written in
+// this call -- link_src only names bytes below the output length of an exported block with status
+// 0, exactly the entries lz4mi_expand_linked_kernel writes (the array is reused between windows and
+// calls, so a stale entry would otherwise be followed). The chase still checks (1) on every hop and
+// counts its hops against the start index, and ends in LZ4MI_ERR_CROSS_BLOCK for the block instead
+// of spinning if either fails.
+//
+// Output races: the gather writes out[out_off[p] .. + min(out_len, out_cap)) of the exported blocks
+// with status 0; link_src classifies exactly those bytes as unresolved, so no kHist pointer names a
+// byte this window's gather writes. Stored blocks (LZ4MI_FRAME_WORDS) are copied by
+// lz4mi_linked_stored_kernel, which precedes the gather on the stream.
+constexpr int32_t kStCross = -9, kStArg = -101, kStRange = -8;   // include/lz4mi.h
+constexpr uint32_t kSpanMax = 1u << 30;
+
+// xl: the window's scratch words -- xl[0]: a block of this call has failed (kept across the call's
+// windows), xl[2..3] / xl[4..5]: win[0] / win[1], then nblocks lengths (in_len without the stored
+// bit; 0 for a block that is not parsed) and nblocks literal bases.
+// One workgroup: the window's lowest offsets, then per block the limits, the slot order, the spans;
+// stored, refused and (after a failure in an earlier window) all blocks are marked not exported.
+__global__ __launch_bounds__(256) void lz4mi_linked_prep_kernel(ExpArgs a, uint32_t nblocks, uint32_t x_in_max, int fw,
+                                                                int has_prev, uint32_t* xl, uint32_t* xcnt_w) {
+    __shared__ unsigned long long lo[2];
+    if (threadIdx.x == 0) lo[0] = lo[1] = ~0ull;
+    __syncthreads();
+    unsigned long long mi = ~0ull, mo = ~0ull;
+    for (uint32_t b = threadIdx.x; b < nblocks; b += 256) {
+        mi = min(mi, (unsigned long long)a.in_off[b]);
+        mo = min(mo, (unsigned long long)a.out_off[b]);
+    }
+    atomicMin(&lo[0], mi);
+    atomicMin(&lo[1], mo);
+    __syncthreads();
+    const uint64_t in_lo = lo[0], out_lo = lo[1];
+    if (threadIdx.x == 0) {
+        ((uint64_t*)(xl + 2))[0] = in_lo;
+        ((uint64_t*)(xl + 2))[1] = out_lo;
+    }
+    const bool failed = xl[0] != 0;
+    uint32_t* wlen = xl + 8;
+    uint32_t* lbase = wlen + nblocks;
+    for (uint32_t b = threadIdx.x; b < nblocks; b += 256) {
+        const uint32_t word = a.in_len[b], cap = a.out_cap[b];
+        const bool stored = fw && (word & 0x80000000u);
+        const uint32_t len = fw ? word & 0x7FFFFFFFu : word;
+        const uint64_t io = a.in_off[b], oo = a.out_off[b];
+        bool bad = !stored && (len > x_in_max || cap > a.x_out_max);
+        if ((b > 0 || has_prev) && a.out_off[(int64_t)b - 1] + a.out_cap[(int64_t)b - 1] > oo) bad = true;
+        if (io - in_lo + len >= kSpanMax || oo - out_lo + cap + 65536 >= kSpanMax) bad = true;
+        int32_t st = 0;
+        if (failed) st = kStCross;
+        else if (bad) st = kStArg;
+        else if (stored && len > cap) st = kStRange;
+        const bool parse = !failed && !bad && !stored && len != 0;   // (an empty block: 0 bytes, status 0)
+        wlen[b] = parse ? len : 0u;
+        lbase[b] = (uint32_t)(io - in_lo);
+        if (!parse) xcnt_w[b] = kNotExported;
+        a.status[b] = st;
+        a.out_len[b] = (stored && st == 0) ? len : 0u;
+    }
+}
+
+// One workgroup, after lz4mi_xstatus_kernel and again after the chase: the first block in index
+// order with a status; every block after it gets LZ4MI_ERR_CROSS_BLOCK and no output (the caller
+// can resume there), in this window and, through xl[0], in the call's later ones.
+__global__ __launch_bounds__(256) void lz4mi_linked_fail_kernel(ExpArgs a, uint32_t nblocks, uint32_t* xl) {
+    __shared__ uint32_t first;
+    if (threadIdx.x == 0) first = 0xFFFFFFFFu;
+    __syncthreads();
+    uint32_t m = 0xFFFFFFFFu;
+    for (uint32_t b = threadIdx.x; b < nblocks; b += 256)
+        if (a.status[b] != 0) m = min(m, b);
+    if (m != 0xFFFFFFFFu) atomicMin(&first, m);
+    __syncthreads();
+    const uint32_t f = first;
+    if (f == 0xFFFFFFFFu) return;
+    for (uint32_t b = threadIdx.x; b < nblocks; b += 256)
+        if (b > f) {
+            a.status[b] = kStCross;
+            a.out_len[b] = 0;
+        }
+    if (threadIdx.x == 0) xl[0] = 1u;
+}
+
+// The stored blocks of a frame (LZ4MI_FRAME_WORDS) before the first failure: copied after the
+// statuses are known and before the gather reads them. Workgroup (c, b): 64 KiB pieces c, c + 64, ...
+__global__ __launch_bounds__(256) void lz4mi_linked_stored_kernel(ExpArgs a, const uint32_t* word) {
+    const uint32_t b = blockIdx.y;
+    const uint32_t w = word[b];
+    if (!(w & 0x80000000u) || a.status[b] != 0) return;
+    const uint32_t len = min(w & 0x7FFFFFFFu, a.out_cap[b]);
+    const uint8_t* src = a.in + a.in_off[b];
+    uint8_t* dst = a.out + a.out_off[b];
+    for (uint64_t p0 = (uint64_t)blockIdx.x << 16; p0 < len; p0 += (uint64_t)gridDim.x << 16) {
+        const uint32_t end = (uint32_t)min((uint64_t)len, p0 + 65536);
+        for (uint32_t p = (uint32_t)p0 + threadIdx.x * 16; p < end; p += 256 * 16) {
+            if (p + 16 <= end && (((uintptr_t)(dst + p)) & 15) == 0) {
+                uint4 r;
+                __builtin_memcpy(&r, src + p, 16);
+                *(uint4*)(dst + p) = r;
+            } else {
+                for (uint32_t q = p; q < end && q < p + 16; ++q) dst[q] = src[q];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kXThreads) void lz4mi_expand_linked_kernel(ExpArgs a) { expand_body<true>(a); }
+__global__ __launch_bounds__(kXThreads) void lz4mi_jump_linked_kernel(ExpArgs a, int r) { jump_body<true>(a, r); }
+__global__ __launch_bounds__(kXThreads) void lz4mi_gather_linked_kernel(ExpArgs a) { gather_body<true>(a); }
+
+// The linked chase (the termination argument: above). A chain that breaks an invariant ends the
+// block with LZ4MI_ERR_CROSS_BLOCK (lz4mi_linked_fail_kernel then runs again); its pointer stays
+// unresolved and is not gathered.
+__global__ __launch_bounds__(kXThreads) void lz4mi_chase_linked_kernel(ExpArgs a) {
+  if (a.flags[kJumpRounds] == 0) return;
+  X_TILES(a) {
+    uint32_t wbase = 0;
+    const uint32_t b = X_B(a), t = X_T(a);
+    const uint32_t n = x_wave(a, b, t, wbase);
+    if (!n || *done_flag(a, b, t)) continue;
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t* Q = a.ptr;
+    const uint32_t wb = b * a.x_out_max;
+    for (int k = 0; k < kXBytes; ++k) {
+        const uint32_t x = wbase + lane + 64 * k;
+        if (x >= n) break;
+        uint32_t v = Q[wb + x];
+        if (v >= kUnres) continue;
+        uint32_t at = wb + x, hops = 0;
+        bool ok = true;
+        while (v < kUnres) {
+            if (v >= at || ++hops > wb + x + 1u) {   // not strictly lower / more hops than indices below the start
+                ok = false;
+                break;
+            }
+            at = v;
+            v = Q[v];
+        }
+        if (ok) {
+            Q[wb + x] = v;
+        } else {
+            a.status[b] = kStCross;
+            a.out_len[b] = 0;
+        }
     }
   }
 }
@@ -515,5 +722,79 @@ extern "C" hipError_t lz4mi_launch_expand(const uint8_t* in, const uint64_t* in_
     for (int r = 0; r < kJumpRounds; ++r) hipLaunchKernelGGL(lz4mi_jump_kernel, grid, dim3(kXThreads), 0, stream, a, r);
     hipLaunchKernelGGL(lz4mi_chase_kernel, grid, dim3(kXThreads), 0, stream, a);
     hipLaunchKernelGGL(lz4mi_gather_kernel, grid, dim3(kXThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+// Linked mode, before the parse: the window's bases and which blocks are parsed (xl: see
+// lz4mi_linked_prep_kernel; 8 + 2 * nblocks words).
+extern "C" hipError_t lz4mi_launch_linked_prep(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                               uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                               uint32_t* out_len, int32_t* status, uint32_t nblocks, uint32_t x_in_max,
+                                               uint32_t x_out_max, int fw, int has_prev, uint32_t* xl, uint32_t* xcnt,
+                                               hipStream_t stream) {
+    using namespace lz4mi;
+    ExpArgs a{};
+    a.in = in;
+    a.in_off = in_off;
+    a.in_len = in_len;
+    a.out = out;
+    a.out_off = out_off;
+    a.out_cap = out_cap;
+    a.out_len = out_len;
+    a.status = status;
+    a.x_out_max = x_out_max;
+    hipLaunchKernelGGL(lz4mi_linked_prep_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, x_in_max, fw, has_prev, xl,
+                       xcnt);
+    return hipGetLastError();
+}
+
+// The output phase of a linked window (after the parse of the blocks lz4mi_linked_prep_kernel left
+// exported): checks (absolute positions; no cross-block check), statuses, the first failing block,
+// the stored blocks, then expand, jump rounds, chase and gather over the window's pointer array.
+extern "C" hipError_t lz4mi_launch_expand_linked(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_words,
+                                                 uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
+                                                 const uint8_t* dict, uint32_t dict_len, uint32_t* out_len,
+                                                 int32_t* status, const uint4* xseq, const uint32_t* xcnt,
+                                                 lz4mi::SegRec* xrec, uint32_t nseg, uint32_t xseq_stride, uint32_t* ptr,
+                                                 uint32_t x_out_max, uint32_t* aux, uint32_t* xl, int fw,
+                                                 uint32_t nblocks, hipStream_t stream) {
+    using namespace lz4mi;
+    if (nblocks == 0) return hipSuccess;
+    if ((x_out_max & (x_out_max - 1)) || x_out_max < kTile || (uint64_t)nblocks * x_out_max > (1ull << 31))
+        return hipErrorInvalidValue;
+    uint32_t* flags = aux;
+    uint32_t* best = flags + 32;
+    uint32_t* redo = best + ((nblocks + 63) & ~63u);
+    uint8_t* done = (uint8_t*)(redo + ((nblocks + 63) & ~63u));
+    ExpArgs a{in, in_off, xl + 8, out, out_off, out_cap, dict, dict_len, out_len, status, xseq, xcnt, xrec, nseg,
+              xseq_stride, ptr, x_out_max, done, flags, best, nblocks * (x_out_max / kTile),
+              (uint32_t)__builtin_ctz(x_out_max / kTile), xl + 8 + nblocks, (const uint64_t*)(xl + 2)};
+    hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t) * 32, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(done, 0, (size_t)nblocks * (x_out_max / kXBytes), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lz4mi_xbase_kernel, dim3(nblocks), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(lz4mi_xcheck_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a, 0);
+    hipLaunchKernelGGL(lz4mi_xstatus_kernel, dim3(nblocks), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(lz4mi_linked_fail_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, xl);
+    if (fw) hipLaunchKernelGGL(lz4mi_linked_stored_kernel, dim3(64, nblocks), dim3(256), 0, stream, a, in_words);
+    const dim3 grid(min(a.ntiles, kXGrid));
+    hipLaunchKernelGGL(lz4mi_expand_linked_kernel, grid, dim3(kXThreads), 0, stream, a);
+    for (int r = 0; r < kJumpRounds; ++r)
+        hipLaunchKernelGGL(lz4mi_jump_linked_kernel, grid, dim3(kXThreads), 0, stream, a, r);
+    hipLaunchKernelGGL(lz4mi_chase_linked_kernel, grid, dim3(kXThreads), 0, stream, a);
+    hipLaunchKernelGGL(lz4mi_linked_fail_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, xl);
+    hipLaunchKernelGGL(lz4mi_gather_linked_kernel, grid, dim3(kXThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+// The failure rule alone, over statuses the batch kernel wrote one block per launch (the linked
+// call's last resort, lz4mi_capi.cpp linked_launch).
+extern "C" hipError_t lz4mi_launch_linked_fail(uint32_t* out_len, int32_t* status, uint32_t nblocks, uint32_t* xl,
+                                               hipStream_t stream) {
+    using namespace lz4mi;
+    ExpArgs a{};
+    a.out_len = out_len;
+    a.status = status;
+    hipLaunchKernelGGL(lz4mi_linked_fail_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, xl);
     return hipGetLastError();
 }

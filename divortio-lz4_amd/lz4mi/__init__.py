@@ -30,6 +30,7 @@ XXH_STANDARD = 0x4
 XXH_LEN64 = 0x10
 BLOCK_CHECKSUM = 0x20
 FRAME_WORDS = 0x40
+LINKED = 0x80
 
 GEN_RANDOM, GEN_REPETITIVE, GEN_TILES216 = 0, 1, 2
 GENERATORS = {"random": GEN_RANDOM, "repetitive": GEN_REPETITIVE, "tiles216": GEN_TILES216}
@@ -319,8 +320,11 @@ def host_decoded_size(comp, in_off=0, in_size=None):
     return int(st.value), int(r)
 
 
-def decompress_blocks(blocks, out_sizes=None, js_compat=False, dictionary=None, js_exact=False):
+def decompress_blocks(blocks, out_sizes=None, js_compat=False, dictionary=None, js_exact=False, linked=False):
     """Independent compressed blocks -> (statuses, outputs) (GPU).
+    linked: the blocks may reference the output of the blocks before them (LZ4MI_LINKED: the
+    blocks of a dependent frame in order; the outputs lie back to back); after the first
+    failing block every later one reports ERR_CROSS_BLOCK. Spec mode only.
     out_sizes=None: the sizes are measured first (decoded_sizes) and the blocks decoded at them;
     a block the size pass fails keeps that status and decodes to nothing.
     js_compat: the serial reference-exact kernel; js_exact: the parallel spec
@@ -331,7 +335,7 @@ def decompress_blocks(blocks, out_sizes=None, js_compat=False, dictionary=None, 
         ok = mst == OK
         st, outs, out_len = decompress_blocks([b if k else b"" for b, k in zip(blocks, ok)],
                                               [int(z) if k else 0 for z, k in zip(msz, ok)], js_compat=js_compat,
-                                              dictionary=dictionary, js_exact=js_exact)
+                                              dictionary=dictionary, js_exact=js_exact, linked=linked)
         st = np.where(ok, st, mst).astype(np.int32)
         return st, outs, out_len
     arrs = [_u8(b) for b in blocks]
@@ -351,7 +355,7 @@ def decompress_blocks(blocks, out_sizes=None, js_compat=False, dictionary=None, 
     d = _u8(dictionary)
     _check(lib().lz4mi_decompress_blocks(_p(src), _p(in_off), _p(in_len), _p(out), _p(out_off), _p(out_cap),
                                          _p(d), 0 if d is None else d.size, _p(out_len), _p(status), n,
-                                         _dec_flags(js_compat, js_exact), None))
+                                         _dec_flags(js_compat, js_exact) | (LINKED if linked else 0), None))
     outs = [out[int(o):int(o) + min(int(l), int(c))].copy() for o, l, c in zip(out_off, out_len, out_cap)]
     return status, outs, out_len
 
@@ -398,14 +402,16 @@ def xxh32_blocks(blocks, seed=0, standard=False):
 # handle (int, e.g. torch.cuda.current_stream().cuda_stream). Async.
 def decompress_blocks_dev(in_ptr, in_off_ptr, in_len_ptr, out_ptr, out_off_ptr, out_cap_ptr, out_len_ptr,
                           status_ptr, nblocks, stream=0, js_compat=False, dict_ptr=None, dict_len=0,
-                          frame_words=False, js_exact=False):
+                          frame_words=False, js_exact=False, linked=False):
     """Batch decode on device pointers. frame_words: in_len holds frame size words (bit 31 =
     stored block, copied in the same launch; include/lz4mi.h LZ4MI_FRAME_WORDS). js_exact: the
-    reference decoder's bytes (LZ4MI_JS_EXACT, the JS layer's default)."""
+    reference decoder's bytes (LZ4MI_JS_EXACT, the JS layer's default). linked: dependent blocks
+    in ascending, disjoint slots (LZ4MI_LINKED, spec mode)."""
     _check(lib().lz4mi_decompress_blocks(in_ptr, in_off_ptr, in_len_ptr, out_ptr, out_off_ptr, out_cap_ptr,
                                          dict_ptr, dict_len, out_len_ptr, status_ptr, nblocks,
                                          DEVICE_PTRS | _dec_flags(js_compat, js_exact) |
-                                         (FRAME_WORDS if frame_words else 0), stream or None))
+                                         (FRAME_WORDS if frame_words else 0) | (LINKED if linked else 0),
+                                         stream or None))
 
 
 def decoded_sizes_dev(in_ptr, in_off_ptr, in_len_ptr, out_len_ptr, status_ptr, nblocks, stream=0, frame_words=False):
@@ -425,12 +431,14 @@ def xxh32_blocks_dev(in_ptr, off_ptr, len_ptr, hashes_ptr, nblocks, seed=0, stre
                                     DEVICE_PTRS | (XXH_STANDARD if standard else 0), stream or None))
 
 
-def frame_decompress_dev(frame_ptr, frame_len, out_ptr, out_cap, stream=0, js_exact=False):
+def frame_decompress_dev(frame_ptr, frame_len, out_ptr, out_cap, stream=0, js_exact=False, linked=False):
     """Decode a device-resident LZ4 frame into out (device pointers): returns the info dict
-    (include/lz4mi.h lz4mi_frame_decompress); raises if the frame needs the host path."""
+    (include/lz4mi.h lz4mi_frame_decompress); raises if the frame needs the host path.
+    linked: the compressed blocks go in one linked call (LZ4MI_LINKED, not with js_exact)."""
     info = np.zeros(8, dtype=np.int64)
     _check(lib().lz4mi_frame_decompress(frame_ptr, frame_len, out_ptr, out_cap, info.ctypes.data,
-                                        DEVICE_PTRS | (JS_EXACT if js_exact else 0), stream or None))
+                                        DEVICE_PTRS | (JS_EXACT if js_exact else 0) | (LINKED if linked else 0),
+                                        stream or None))
     keys = ("status", "flg", "content_size", "written", "stored_blocks", "checksum_pos", "block_max", "overflow")
     return dict(zip(keys, (int(x) for x in info)))
 

@@ -826,12 +826,14 @@ def _verify_content_checksum(frame, pos, out):
         raise lz4mi.Lz4miError(lz4mi.ERR_CHECKSUM)
 
 
-def _decode_measured(frame, head, js_exact, s):
+def _decode_measured(frame, head, js_exact, s, linked=False):
     """The measured route of decompress_frame_device: index the frame's blocks on the device,
     measure every block's decoded size in one launch (lz4mi_decoded_sizes), lay the output out
     at the exact positions (exclusive prefix sum on the device) and decode all blocks in one
     batch. Returns (output, position of the content checksum), or None when the frame has to
-    go to the host path so that its first error and message stay what they were."""
+    go to the host path so that its first error and message stay what they were.
+    linked (the "linked" route, spec mode): the batch is one LZ4MI_LINKED call, so the blocks may
+    depend on each other (a block's size does not depend on the bytes before it)."""
     import torch
     import lz4mi
     dev = frame.device
@@ -880,9 +882,9 @@ def _decode_measured(frame, head, js_exact, s):
         status = torch.zeros(nb, dtype=torch.int32, device=dev)
         lz4mi.decompress_blocks_dev(frame.data_ptr(), pay.data_ptr(), word.data_ptr(), out.data_ptr(),
                                     out_off.data_ptr(), sizes.data_ptr(), out_len.data_ptr(), status.data_ptr(), nb,
-                                    s.cuda_stream, frame_words=True, js_exact=js_exact)
+                                    s.cuda_stream, frame_words=True, js_exact=js_exact, linked=linked)
         st = status.cpu().numpy()
-        if ((st != 0) & (st != lz4mi.ERR_CROSS_BLOCK)).any():
+        if ((st != 0) & (st != lz4mi.ERR_CROSS_BLOCK)).any() or (linked and (st != 0).any()):
             return None
         # blocks that read earlier blocks' output: every block before them is final now; each alone, in order
         # (the same bytes as the host path's 64 KiB window: a match offset has 16 bits, so it never reaches
@@ -899,9 +901,10 @@ def _decode_measured(frame, head, js_exact, s):
     return out[:total], int(h[5])
 
 
-def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=None, report=None):
+def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=None, report=None, linked=False):
     """Decode a device-resident frame (1-D uint8 CUDA tensor) on its GPU. Three routes, in this
-    order; `report` (a dict, optional) receives {"route": "layout" | "measured" | "host"}:
+    order; `report` (a dict, optional) receives {"route": "layout" | "measured" | "host"}
+    (with `linked`: "layout" | "linked" | "host"):
      - layout: the header and the block walk run on the device (lz4mi_frame_decompress), stored
        blocks are copied and the compressed ones decoded in one batch at the positions of the
        reference encoder's layout (content size present, every block but the last fills block_max);
@@ -913,6 +916,10 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
        lands elsewhere than in a contiguous result);
      - host: everything else (dependent blocks, the empty frame, frames with an error in a
        block), block by block through the host-buffer path, as bufferDecompress.js does.
+    linked=True (ignored with js_exact): dependent blocks are decoded in one call too
+    (LZ4MI_LINKED): the layout route passes the flag, and a frame the layout walk declines takes
+    the route "linked" whatever FLG 0x20 says -- the measured route with one linked batch; the
+    host route stays the last resort (the empty frame, frames with an error in a block).
     The content checksum (FLG 0x04) is verified on the host, streamed piece by piece. Returns
     the content as a uint8 CUDA tensor. Raises lz4mi.Lz4miError with the reference's message
     for the frame's first error."""
@@ -928,21 +935,24 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
     out = torch.empty(max(1, size), dtype=torch.uint8, device=frame.device)
     if report is None:
         report = {}
+    lk = bool(linked) and not js_exact
     try:
         info = lz4mi.frame_decompress_dev(frame.data_ptr(), frame.numel(), out.data_ptr(), size, s.cuda_stream,
-                                          js_exact=js_exact)
+                                          js_exact=js_exact, linked=lk)
     except lz4mi.Lz4miError as e:
         if e.status != lz4mi.ERR_ARG:
             raise
         del out
         got = None
-        if head.size > 4 and head[4] & 0x20 and not (js_exact and size == 0):
+        if lk:
+            got = _decode_measured(frame, head, False, s, linked=True)
+        elif head.size > 4 and head[4] & 0x20 and not (js_exact and size == 0):
             got = _decode_measured(frame, head, js_exact, s)
         if got is None:
             report["route"] = "host"
             host = decompress_frame_host(frame.cpu().numpy(), js_exact=js_exact, verify_checksum=verify_checksum)
             return torch.from_numpy(host).to(frame.device)
-        report["route"] = "measured"
+        report["route"] = "linked" if lk else "measured"
         res, pos = got
         if verify_checksum and head[4] & 0x04:
             s.synchronize()

@@ -72,6 +72,9 @@ extern "C" {
                                     is the frame's raw size word; bit 31 set = a stored block, whose bytes are
                                     copied in the same launch (bufferDecompress.js:173-180: LZ4MI_ERR_RANGE when
                                     they exceed out_cap[b], the reference's result.set RangeError) */
+#define LZ4MI_LINKED 0x80u       /* lz4mi_decompress_blocks, lz4mi_frame_decompress (spec mode): the blocks may
+                                    reference the output of the blocks before them (dependent-block frames);
+                                    the whole batch is decoded in one call. Contract: lz4mi_decompress_blocks. */
 
 /* Largest block the kernels accept (the reference's largest block size is 4 MiB;
  * raw calls may pass more, up to 2^31-1 like the reference's `|0` arithmetic). */
@@ -109,6 +112,27 @@ const char* lz4mi_build_id(void);
  * then `dict`, exactly as the reference). LZ4MI_JS_COMPAT decodes the blocks
  * in order on one lane with the reference's byte-level behaviour.
  * Returns LZ4MI_OK when the batch ran (per-block errors are in status[]).
+ *
+ * LZ4MI_LINKED (spec mode; with LZ4MI_JS_COMPAT or LZ4MI_JS_EXACT: LZ4MI_ERR_ARG): dependent blocks
+ * in one call. Precondition: the output slots are ascending and disjoint, out_off[b] + out_cap[b]
+ * <= out_off[b+1]; gaps are allowed, the caller's bytes there are final. Result: the bytes,
+ * out_len[] and status[] that nblocks successive nblocks == 1 calls in index order on the same
+ * `out` would give: a back-reference below a block's start reads the earlier block's freshly
+ * decoded bytes where it falls inside an earlier slot of the batch (up to that block's out_len),
+ * the caller's bytes of `out` otherwise, and the tail of `dict` below out[0]. The capacity,
+ * dictionary-bounds and other checks keep their absolute-position meaning; LZ4MI_ERR_CROSS_BLOCK is
+ * not a check here. After a failure: the first block in index order with status != 0 keeps it;
+ * every later block gets LZ4MI_ERR_CROSS_BLOCK, out_len 0 and is not written (the caller can resume
+ * from the failing block). Limits: out_cap[b] <= 4 MiB and in_len[b] <= lz4mi_compress_bound(4 MiB);
+ * a block past them, or a slot that breaks the precondition, is LZ4MI_ERR_ARG for the call with
+ * host pointers and status LZ4MI_ERR_ARG for that block (then the after-failure rule) with device
+ * pointers -- as is a block of a device-pointer batch whose slots are spread so far that a pass
+ * cannot address them (about 1 GiB of `in` or `out` per ~240 blocks of 4 MiB). Valid with
+ * LZ4MI_DEVICE_PTRS (asynchronous, nothing read back) and with host pointers (the whole output range
+ * is staged: gaps and unused slot tails are history); with LZ4MI_FRAME_WORDS on device pointers a
+ * stored block is copied in the same call before anything reads it. Any nblocks: the call cuts the
+ * batch into passes in index order on the one stream, as many blocks each as the scratch cap
+ * (LZ4MI_SMALL_SCRATCH_MB, compared with the real allocation) and the pointer encodings allow.
  */
 int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
                                 uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
@@ -228,7 +252,10 @@ int32_t lz4mi_frame_pack(const uint8_t* raw, const uint64_t* raw_off, const uint
  * header) or 0; [1] FLG; [2] content size; [3] bytes written; [4] stored blocks; [5] position
  * of the content checksum (after the EndMark) when FLG has 0x04; [6] block max size (BD).
  * The content checksum (one serial XXH32 chain) is the caller's to verify.
- * flags: LZ4MI_DEVICE_PTRS (required) | LZ4MI_JS_EXACT (reference-exact; default LZ4 spec).
+ * flags: LZ4MI_DEVICE_PTRS (required) | LZ4MI_JS_EXACT (reference-exact; default LZ4 spec)
+ * | LZ4MI_LINKED (spec mode only, with LZ4MI_JS_EXACT: LZ4MI_ERR_ARG): the compressed blocks are
+ * issued as one linked batch after the stored copies, so a dependent-block frame needs no launch
+ * per block; without it dependent blocks are decoded one per launch, in order.
  * Synchronous (reads the header and the block lists back). Returns LZ4MI_ERR_ARG for frames
  * this path does not take (no content size, a block layout other than the reference encoder's,
  * out_cap too small): decode those with the host-buffer path block by block.
