@@ -3,9 +3,10 @@
 // Replaces decompressBlock (reference src/block/blockDecompress.js:30-275) for
 // batches of independent blocks. Semantics follow the reference exactly for
 // spec-valid input (positions absolute in `out`, dictionary below out[0],
-// clipped match writes, the four error strings); LZ4MI_JS_COMPAT selects the
-// serial kernel (lz4mi_decompress_serial.hip), which also reproduces the
-// reference's double-copy-tail rewrite.
+// clipped match writes, the four error strings). The reference's double-copy-
+// tail rewrite is reproduced by LZ4MI_JS_EXACT (this kernel plus
+// the in-chunk replay, f1_fixup) and by LZ4MI_JS_COMPAT (the blocks in order on
+// one lane, lz4mi_decompress_serial.hip).
 //
 // One wave64 per block, all 4096 blocks of a batch resident at once
 // (< 10 KiB LDS, <= 128 VGPRs -> 16 waves per CU). Per 1 KiB chunk of the
@@ -21,8 +22,12 @@
 //     neighbour is settled). The result is the exact serial parse. Walks
 //     start 256 bytes back: inside long literal runs a walk can take a while
 //     to fall onto the true chain, and every unsettled lane costs a pass.
-//  4. Sequence table in LDS (literal source, lengths, offset, output start by
-//     wave prefix sums) and errors in the reference's order.
+//  4. Sequence table in LDS, built sequence-major: the lanes list their tokens'
+//     positions compactly (lane l's at base(l) + j), then lane l of row i takes
+//     sequence 64i+l, reads its fields (literal source, lengths, offset), gets
+//     its output start from a row prefix sum plus the carry of the rows before
+//     and writes its entry once. Errors in the reference's order: a 32-bit test
+//     per row pair, the exact checks only from the first flagged pair on.
 //  5. Output, sequence-parallel (lane l takes sequence 64i+l), every run
 //     written with exact-width unaligned 16/8/4/2/1-byte pieces (the last
 //     16-byte piece of a run overlaps its predecessor instead of spilling),
@@ -1418,101 +1423,146 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
 
         PROF(2);
         // ---- 4. sequence table -----------------------------------------
-        // A lane's tokens (those of its segment, in order) four at a time, each group's
-        // byte reads issued together (two LDS round trips per group, not per token);
-        // output starts by wave prefix sums; errors in the reference's order.
+        // Sequence-major from a compact token list: every lane writes the positions of its
+        // segment's tokens at base + j, then lane l of row i takes sequence k = 64 i + l, reads
+        // its fields, gets its output start from a row scan plus the carry of the rows before,
+        // and writes its entry once. Two rows per step, their byte reads issued together (three
+        // LDS round trips per step). Errors in the reference's order: a 32-bit test per row pair,
+        // and the exact 64-bit checks only from the first flagged pair on.
         const uint32_t cnt = __popc(vis) - ((cut && lane == last_lane) ? 1u : 0u);
         const uint32_t incl = wave_incl_scan(cnt, lane);
         const uint32_t base = incl - cnt;
         const uint32_t nseq = lane_of(incl, kWave - 1);
-        uint32_t run = 0;
-        bool rerun = false;   // a true token's match length runs on past one byte (fast table)
+        uint16_t* const tl = (uint16_t*)S.pms;   // (idle until the output phase; kMaxSeq * 2 bytes)
+        static_assert(sizeof(uint16_t) * (kMaxSeq + 2 * kWave) <= sizeof(S.pms), "token list fits in the pending starts");
         {
             uint32_t m = vis;
-            for (uint32_t g = 0; __ballot(g < cnt) != 0; g += 4) {
-                uint32_t p[4], tok[4], b1[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    p[j] = g + j < cnt ? seg0 + __builtin_ctz(m) : seg0;
-                    if (g + j < cnt) m &= m - 1;
-                    tok[j] = s[p[j]];
-                    b1[j] = s[p[j] + 1];
-                }
-                uint32_t q[4], lit[4], ll[4], o0[4], o1[4], mb[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t x1 = (tok[j] >> 4) == 15 ? 1u : 0u;
-                    ll[j] = x1 ? 15u + b1[j] : tok[j] >> 4;
-                    lit[j] = p[j] + 1 + x1;
-                    q[j] = lit[j] + ll[j];
-                    // offset bytes inside the window (q + 2 <= kLim: a sequence may end on its last byte,
-                    // as next_token accepts; s[q + 2] is still staged) -- past it only a long literal run
-                    // (slow below)
-                    const uint32_t qa = q[j] + 2 <= (uint32_t)kLim ? q[j] : 0u;
-                    o0[j] = s[qa];
-                    o1[j] = s[qa + 1];
-                    mb[j] = s[qa + 2];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (g + j >= cnt) continue;
-                    uint32_t llj = ll[j], litj = lit[j], qj = q[j], off = 0, ml = 0;
-                    if ((tok[j] >> 4) == 15 && b1[j] == 255) {   // literal length field of 2+ bytes
-                        uint32_t r = p[j] + 1, bb;
-                        llj = 15;
-                        do { bb = s[r++]; llj += bb; } while (bb == 255);
-                        litj = r;
-                        qj = r + llj;
-                        if (qj < rem) { o0[j] = s[qj]; o1[j] = s[qj + 1]; mb[j] = s[qj + 2]; }
-                    }
-                    if (qj < rem) {
-                        off = o0[j] | (o1[j] << 8);
-                        ml = tok[j] & 15;
-                        if (ml == 15) {
-                            if (mb[j] != 255) {
-                                ml += mb[j];
-                            } else {
-                                rerun |= fast_tab;
-                                uint32_t r = qj + 2, bb;
-                                do { bb = s[r++]; ml += bb; } while (bb == 255 && r < (uint32_t)kLim);
-                            }
-                        }
-                        ml += 4;
-                    }
-                    const uint32_t k = base + g + j;
-                    S.t_seq[k] = make_uint4(run, litj | (llj << 16), off | (ml << 16), 0u);
-                    run += llj + ml;
-                }
+            for (uint32_t j = 0; j < cnt; ++j) {
+                tl[base + j] = (uint16_t)(seg0 + __builtin_ctz(m));
+                m &= m - 1;
             }
         }
-        if (__ballot(rerun)) {   // the fast table assumed a one-byte match length field
-            fast_tab = false;
-            wait_vmem();          // (no load in flight into the parse: its registers are free)
-            settle(pf0);
-            settle(pf1);
-            __syncthreads();
-            goto parse;
-        }
-        const uint32_t lincl = wave_incl_scan(run, lane);
-        const uint32_t lbase = lincl - run;
-        const int64_t total = lane_of(lincl, kWave - 1);
-        uint32_t first_err = 0xFFFFFFFFu;
-        for (uint32_t g = 0; __ballot(g < cnt) != 0; g += 4) {
-            SeqInfo q[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) q[j] = seq_info(S, base + (g + j < cnt ? g + j : 0u));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (g + j >= cnt) continue;
-                const uint32_t k = base + g + j;
-                const int64_t os = c.O + lbase + (uint32_t)q[j].out;
-                S.t_seq[k].x = (uint32_t)os;
-                const uint32_t e = seq_err<XP>(c, xp, os, (int64_t)c.ip + q[j].lit, q[j].ll, q[j].off, q[j].ml);
-                if (e && first_err == 0xFFFFFFFFu) first_err = (k << 3) | e;
-            }
-        }
-        first_err = wave_min(first_err);
         __syncthreads();
+        // The 32-bit form of the five checks. With c.O <= c.cap (else every row is checked exactly),
+        // c.cap < 2^31, a table's output under 2^26 bytes (at most kMaxSeq sequences of under 2^17
+        // bytes each: both lengths are 16-bit fields of the entry) and offsets under 2^16, every sum
+        // below stays under 2^32, so the test is exact:
+        //   1  out + ll > cap                  <=>  X > capr, X = (out - c.O) + ll, capr = cap - c.O
+        //   2  ip + lit + ll > in_len          <=>  lit + ll > rem
+        //   3  off == 0, 4 off > out_off + out + ll + dict_len, 5 isolate and off > out + ll
+        //                                      <=>  off - 1 >= L45 + X (wrapping for off = 0), with
+        //      L45 = c.O + (isolate ? 0 : min(out_off + dict_len, 2^16)): past 2^16 check 4 cannot fail
+        // An exported segment (relative positions) has checks 2 and 3 only.
+        const bool rel = XP && xp;
+        const bool exact_all = !rel && c.O > (int64_t)c.cap;
+        const uint32_t capr = rel || exact_all ? 0xFFFFFFFFu : (uint32_t)(c.cap - (int32_t)c.O);
+        const int64_t d4 = c.out_off + c.dict_len;
+        const uint32_t L45 = rel || exact_all ? 0x80000000u
+                                              : (uint32_t)c.O + (c.isolate ? 0u : (uint32_t)(d4 < 65536 ? d4 : 65536));
+        uint32_t carry = 0;   // output bytes of the rows before
+        uint32_t first_err = 0xFFFFFFFFu;
+        uint32_t flagged = 0xFFFFFFFFu;   // first rows the 32-bit test flags
+        constexpr int kRows = 2;
+        for (uint32_t i0 = 0; i0 < nseq; i0 += kRows * kWave) {
+            uint32_t p[kRows], tok[kRows], b1[kRows];
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) {
+                const uint32_t k = i0 + kWave * r + lane;
+                p[r] = k < nseq ? tl[k] : 0u;
+            }
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) {
+                tok[r] = s[p[r]];
+                b1[r] = s[p[r] + 1];
+            }
+            uint32_t q[kRows], lit[kRows], ll[kRows], o0[kRows], o1[kRows], mb[kRows];
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) {
+                const uint32_t x1 = (tok[r] >> 4) == 15 ? 1u : 0u;
+                ll[r] = x1 ? 15u + b1[r] : tok[r] >> 4;
+                lit[r] = p[r] + 1 + x1;
+                q[r] = lit[r] + ll[r];
+                // offset bytes inside the window (q + 2 <= kLim: a sequence may end on its last byte,
+                // as next_token accepts; s[q + 2] is still staged) -- past it only a long literal run
+                // (slow below)
+                const uint32_t qa = q[r] + 2 <= (uint32_t)kLim ? q[r] : 0u;
+                o0[r] = s[qa];
+                o1[r] = s[qa + 1];
+                mb[r] = s[qa + 2];
+            }
+            uint32_t off[kRows], ml[kRows];
+            bool rerun = false;   // a true token's match length runs on past one byte (fast table)
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) {
+                const bool live = i0 + kWave * r + lane < nseq;
+                off[r] = 0;
+                ml[r] = 0;
+                if (!live) {
+                    ll[r] = 0;
+                    continue;
+                }
+                uint32_t qj = q[r];
+                if ((tok[r] >> 4) == 15 && b1[r] == 255) {   // literal length field of 2+ bytes
+                    uint32_t t = p[r] + 1, bb, llj = 15;
+                    do { bb = s[t++]; llj += bb; } while (bb == 255);
+                    ll[r] = llj;
+                    lit[r] = t;
+                    qj = t + llj;
+                    if (qj < rem) { o0[r] = s[qj]; o1[r] = s[qj + 1]; mb[r] = s[qj + 2]; }
+                }
+                if (qj < rem) {
+                    off[r] = o0[r] | (o1[r] << 8);
+                    uint32_t m = tok[r] & 15;
+                    if (m == 15) {
+                        if (mb[r] != 255) {
+                            m += mb[r];
+                        } else {
+                            rerun |= fast_tab;
+                            uint32_t t = qj + 2, bb;
+                            do { bb = s[t++]; m += bb; } while (bb == 255 && t < (uint32_t)kLim);
+                        }
+                    }
+                    ml[r] = m + 4;
+                }
+            }
+            if (__ballot(rerun)) {   // the fast table assumed a one-byte match length field
+                fast_tab = false;
+                wait_vmem();          // (no load in flight into the parse: its registers are free)
+                settle(pf0);
+                settle(pf1);
+                __syncthreads();
+                goto parse;
+            }
+            bool flag = false;
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) {
+                if (r > 0 && i0 + kWave * r >= nseq) break;
+                const uint32_t k = i0 + kWave * r + lane;
+                const uint32_t len = ll[r] + ml[r];
+                const uint32_t sc = wave_incl_scan(len, lane);
+                const uint32_t ro = carry + sc - len;   // output start, relative to c.O
+                carry += lane63(sc);
+                if (k < nseq) {
+                    S.t_seq[k] = make_uint4((uint32_t)c.O + ro, lit[r] | (ll[r] << 16), off[r] | (ml[r] << 16), 0u);
+                    const uint32_t X = ro + ll[r];
+                    flag |= X > capr || lit[r] + ll[r] > rem || (ml[r] != 0 && off[r] - 1u >= L45 + X);
+                }
+            }
+            if (__ballot(flag) != 0 && flagged > i0) flagged = i0;
+        }
+        __syncthreads();
+        // the exact checks, from the first flagged rows on (absent on valid input); the first
+        // failing sequence ends them
+        for (uint32_t i0 = exact_all ? 0u : flagged; i0 < nseq && first_err == 0xFFFFFFFFu; i0 += kWave) {
+            const uint32_t k = i0 + lane;
+            uint32_t e = 0;
+            if (k < nseq) {
+                const SeqInfo q = seq_info(S, k);
+                e = seq_err<XP>(c, xp, c.O + (uint32_t)(q.out - (int32_t)c.O), (int64_t)c.ip + q.lit, q.ll, q.off, q.ml);
+            }
+            first_err = wave_min(e ? (k << 3) | e : 0xFFFFFFFFu);
+        }
+        const int64_t total = carry;
         if (first_err != 0xFFFFFFFFu && !(XP && xp)) { status = err_status(first_err & 7); break; }
 
         PROF(3);
