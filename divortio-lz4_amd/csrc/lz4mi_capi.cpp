@@ -890,7 +890,8 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     uint8_t h[19] = {0};
     LZ4MI_TRY(hipMemcpyAsync(h, frame, std::min<uint64_t>(len, 19), hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipStreamSynchronize(s));
-    // magic and version as the device walk reports them (bufferDecompress.js:59-67)
+    // magic and version as the device walk reports them (bufferDecompress.js:59-67), info[6] included
+    info[6] = 4194304;
     if (len < 4 || le32(h) != 0x184D2204u) {
         info[0] = LZ4MI_ERR_MAGIC;
         return LZ4MI_OK;

@@ -194,7 +194,12 @@ int64_t decompress_block(Arr in, int64_t in_pos, int64_t in_end, OutArr out, int
         if (ll > 0) {
             if (in_pos >= 0 && in_pos + ll <= in.n) {
                 std::memcpy(out.p + out_pos, in.p + in_pos, (size_t)ll);
-            } else {
+            } else if (ll > 32) {
+                // output.set(input.subarray(inPos, inPos + literalLen), outPos) (:82): subarray clips at the
+                // input array's end, and the output bytes behind the clipped copy stay as they were
+                const int64_t have = in_pos < in.n ? in.n - in_pos : 0;
+                for (int64_t k = 0; k < ll && k < have; ++k) out.put(out_pos + k, in.at(in_pos + k));
+            } else {                                               // byte stores (:86-120): undefined -> 0
                 for (int64_t k = 0; k < ll; ++k) out.put(out_pos + k, in.at(in_pos + k));
             }
         }
@@ -305,9 +310,10 @@ extern "C" int64_t lz4mi_host_decompress_block(const uint8_t* in, uint64_t in_to
 // size pass (lz4mi_size.hip). Only the two errors that do not depend on output positions
 // exist here: Malformed Input (:75) and Invalid Offset 0 (:128), Malformed tested first
 // within a sequence. Lengths accumulate in 64 bits.
-extern "C" int64_t lz4mi_host_decoded_size(const uint8_t* in, uint64_t in_total, int64_t in_off, int64_t in_size,
-                                           int32_t* status) {
-    if (!status || (!in && in_total) || in_off < 0 || in_size < 0) return LZ4MI_ERR_ARG;
+// *read_end: the position behind the last length or offset byte the walk read (literals lie inside
+// the block, :75): above in_off + in_size when it read past the block's end.
+static int64_t walk_block(const uint8_t* in, uint64_t in_total, int64_t in_off, int64_t in_size, int32_t* status,
+                          int64_t* read_end) {
     const Arr a{in, (int64_t)in_total};
     int64_t in_pos = in_off;
     const int64_t in_end = in_off + in_size;
@@ -346,10 +352,26 @@ extern "C" int64_t lz4mi_host_decoded_size(const uint8_t* in, uint64_t in_total,
         }
         total += ml + 4;
     }
+    *read_end = in_pos;
     if (total > LZ4MI_MAX_BLOCK) {   // no decode call could be given such a capacity
         *status = LZ4MI_ERR_OUTPUT_TOO_SMALL;
         return 0x7FFFFFFF;
     }
     *status = st;
     return (int64_t)total;
+}
+
+extern "C" int64_t lz4mi_host_decoded_size(const uint8_t* in, uint64_t in_total, int64_t in_off, int64_t in_size,
+                                           int32_t* status) {
+    if (!status || (!in && in_total) || in_off < 0 || in_size < 0) return LZ4MI_ERR_ARG;
+    int64_t read_end = 0;
+    return walk_block(in, in_total, in_off, in_size, status, &read_end);
+}
+
+extern "C" int64_t lz4mi_host_block_read_end(const uint8_t* in, uint64_t in_total, int64_t in_off, int64_t in_size) {
+    if ((!in && in_total) || in_off < 0 || in_size < 0) return LZ4MI_ERR_ARG;
+    int32_t st = 0;
+    int64_t read_end = in_off;
+    walk_block(in, in_total, in_off, in_size, &st, &read_end);
+    return read_end;
 }

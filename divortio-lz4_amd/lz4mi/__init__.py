@@ -45,7 +45,7 @@ EXPORTS = ("lz4mi_status_message", "lz4mi_init", "lz4mi_device_count", "lz4mi_ve
            "lz4mi_build_id", "lz4mi_xxh32_reset", "lz4mi_xxh32_update", "lz4mi_xxh32_digest",
            "lz4mi_frame_decompress", "lz4mi_frame_index", "lz4mi_compress_chain",
            "lz4mi_host_compress_block", "lz4mi_host_compress_chain", "lz4mi_host_decompress_block",
-           "lz4mi_decoded_sizes", "lz4mi_host_decoded_size")
+           "lz4mi_decoded_sizes", "lz4mi_host_decoded_size", "lz4mi_host_block_read_end")
 
 
 class Lz4miError(RuntimeError):
@@ -116,6 +116,8 @@ def lib():
         L.lz4mi_decoded_sizes.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
         L.lz4mi_host_decoded_size.restype = ctypes.c_int64
         L.lz4mi_host_decoded_size.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp]
+        L.lz4mi_host_block_read_end.restype = ctypes.c_int64
+        L.lz4mi_host_block_read_end.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64]
         L.lz4mi_frame_index.restype = ctypes.c_int32
         L.lz4mi_frame_index.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp]
         L.lz4mi_generate_blocks.restype = ctypes.c_int32
@@ -318,6 +320,18 @@ def host_decoded_size(comp, in_off=0, in_size=None):
     if r < 0:
         raise Lz4miError(int(r))
     return int(st.value), int(r)
+
+
+def host_block_read_end(comp, in_off=0, in_size=None):
+    """Where the reference's walk of comp[in_off : in_off + in_size] stops reading (host, no device
+    needed; lz4mi_host_block_read_end): above in_off + in_size when the block reads past its end."""
+    a = _u8(comp)
+    if in_size is None:
+        in_size = a.size - in_off
+    r = lib().lz4mi_host_block_read_end(_p(a), a.size, in_off, in_size)
+    if r < 0:
+        raise Lz4miError(int(r))
+    return int(r)
 
 
 def decompress_blocks(blocks, out_sizes=None, js_compat=False, dictionary=None, js_exact=False, linked=False):

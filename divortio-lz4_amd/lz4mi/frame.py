@@ -826,6 +826,18 @@ def _verify_content_checksum(frame, pos, out):
         raise lz4mi.Lz4miError(lz4mi.ERR_CHECKSUM)
 
 
+def content_size_bound(frame_len):
+    """The largest content size a frame of frame_len bytes is decoded for. A content size sizes the
+    result before a block is looked at, and a damaged header can claim anything (the reference
+    then fails in new Uint8Array, or allocates it). A compressed block of n bytes decodes to fewer
+    than 255 * n bytes (a length byte adds at most 255, and costs a byte), a stored one to n, so
+    255 * frame_len bounds what the frame's bytes can decode to; the reference's
+    largest block (4 MiB) of slack on top, so that a frame cut inside its first record still gives
+    the reference's result, content-size zeros. Above the bound both decompress_frame_host and
+    decompress_frame_device raise ERR_RANGE and allocate nothing."""
+    return 255 * int(frame_len) + 4194304
+
+
 def _decode_measured(frame, head, js_exact, s, linked=False):
     """The measured route of decompress_frame_device: index the frame's blocks on the device,
     measure every block's decoded size in one launch (lz4mi_decoded_sizes), lay the output out
@@ -921,8 +933,10 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
     the route "linked" whatever FLG 0x20 says -- the measured route with one linked batch; the
     host route stays the last resort (the empty frame, frames with an error in a block).
     The content checksum (FLG 0x04) is verified on the host, streamed piece by piece. Returns
-    the content as a uint8 CUDA tensor. Raises lz4mi.Lz4miError with the reference's message
-    for the frame's first error."""
+    the content as a uint8 CUDA tensor: with a content size that many bytes, zeros behind what
+    the blocks wrote (the reference's zero-initialised result). Raises lz4mi.Lz4miError with the
+    reference's message for the frame's first error; a content size above content_size_bound
+    is ERR_RANGE before anything is allocated for it."""
     import torch
     import lz4mi
     # the library binds one device per process: a frame on another device raises ERR_ARG here
@@ -931,18 +945,31 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
     head = frame[:19].cpu().numpy()
     if head.size < 4 or int.from_bytes(head[:4].tobytes(), "little") != 0x184D2204:
         raise lz4mi.Lz4miError(lz4mi.ERR_MAGIC)
-    size = int.from_bytes(head[6:14].tobytes(), "little") if head.size >= 14 and head[4] & 0x08 else 0
-    out = torch.empty(max(1, size), dtype=torch.uint8, device=frame.device)
+    # the content size as the reference reads it: the bytes the frame's end cuts off are 0
+    h14 = np.zeros(14, dtype=np.uint8)
+    h14[:min(14, head.size)] = head[:14]
+    size = int.from_bytes(h14[6:14].tobytes(), "little") if head.size > 4 and head[4] & 0x08 else 0
     if report is None:
         report = {}
+    if ((int(h14[4]) & 0xC0) >> 6) != 1:         # before the content size is looked at, as in the reference
+        raise lz4mi.Lz4miError(lz4mi.ERR_VERSION)
+    if size > content_size_bound(frame.numel()):
+        # checked before the header's claim sizes any allocation: the host route refuses the frame
+        # (ERR_RANGE; the reference's own failure there is the RangeError of new Uint8Array)
+        report["route"] = "host"
+        decompress_frame_host(frame.cpu().numpy(), js_exact=js_exact, verify_checksum=verify_checksum)
+        raise lz4mi.Lz4miError(lz4mi.ERR_RANGE)
     lk = bool(linked) and not js_exact
     try:
+        if head.size < 14 and size:
+            raise lz4mi.Lz4miError(lz4mi.ERR_ARG)   # the size field itself is cut: the host route's frame
+        out = torch.empty(max(1, size), dtype=torch.uint8, device=frame.device)
         info = lz4mi.frame_decompress_dev(frame.data_ptr(), frame.numel(), out.data_ptr(), size, s.cuda_stream,
                                           js_exact=js_exact, linked=lk)
     except lz4mi.Lz4miError as e:
         if e.status != lz4mi.ERR_ARG:
             raise
-        del out
+        out = None
         got = None
         if lk:
             got = _decode_measured(frame, head, False, s, linked=True)
@@ -961,7 +988,13 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
     report["route"] = "layout"
     if info["status"]:
         raise lz4mi.Lz4miError(info["status"])
-    out = out[:info["written"]]
+    # the reference's result is its zero-initialised content-size array, whatever the blocks wrote
+    # (only the frame's last block can fall short on this route): zeros behind it, all of it checksummed
+    out = out[:size]
+    if info["written"] < size:
+        with torch.cuda.stream(s):
+            out[info["written"]:].zero_()
+        s.synchronize()
     if verify_checksum and info["flg"] & 0x04:
         _verify_content_checksum(frame, info["checksum_pos"], out)
     return out
@@ -971,39 +1004,59 @@ def decompress_frame_host(frame, js_exact=False, verify_checksum=True):
     """A frame in host memory decoded block by block through the host-buffer C-ABI path,
     with the reference's two layouts (bufferDecompress.js:97-186): with a content size every
     block is decoded straight into the result at its position (back-references into earlier
-    blocks resolve there); without one, each block is decoded behind the last 64 KiB of output
-    (the reference's rolling window). Returns the content (numpy uint8)."""
+    blocks resolve there); without one, each block is decoded into one 4 MiB workspace kept for
+    the whole frame, the last 64 KiB of output (the reference's rolling window) as its dictionary. With a
+    content size the result is the reference's: content-size bytes, zeros behind what the blocks
+    wrote, and the content checksum is taken over all of them. Returns the content (numpy uint8).
+
+    A block whose declared size runs past the frame's end is decoded with that size, as the
+    reference does (decompressBlock gets the size word, bytes past the array read as 0): on the
+    host decoder (lz4mi_host_decompress_block over the whole frame), so nothing of the declared
+    size is allocated. So is a block whose last offset or length field reaches behind its own end
+    (a size word that is off by a few bytes): the reference reads the frame's bytes there."""
     import lz4mi
-    f = np.asarray(frame, dtype=np.uint8)
+    f = np.ascontiguousarray(frame, dtype=np.uint8)
     try:
         info, blocks = shard.frame_blocks(f)
     except ValueError:
         raise lz4mi.Lz4miError(lz4mi.ERR_MAGIC)
     if ((info["flg"] & 0xC0) >> 6) != 1:
         raise lz4mi.Lz4miError(lz4mi.ERR_VERSION)
-    bmax = info["block_max"]
     size = info["content_size"]
+    if size > content_size_bound(f.size):
+        raise lz4mi.Lz4miError(lz4mi.ERR_RANGE)
+
+    def block(p, n, out, pos, window=None):
+        """decompressBlock(data, p, n, out, pos, window): bytes written."""
+        if p + n >= 2 ** 31:      # inEnd = (inputOffset + inputSize) | 0 is negative: nothing is decoded
+            return 0
+        # the batch decoder's block ends at n (zeros behind it); the reference's reads on in the frame
+        if p + n <= f.size and lz4mi.host_block_read_end(f, p, n) <= p + n:
+            return lz4mi.decompress_raw(f, p, n, out, pos, dictionary=window, js_exact=js_exact)
+        return lz4mi.host_decompress_raw(f, p, n, out, pos, dictionary=window, spec=not js_exact)
+
     if size > 0:
         out = np.zeros(size, dtype=np.uint8)
         pos = 0
         for p, n, stored in blocks:
             if stored:
-                if pos + n > size:
+                seg = f[p:p + n]              # subarray() clips at the frame's end
+                if pos + seg.size > size:
                     raise lz4mi.Lz4miError(lz4mi.ERR_RANGE)
-                out[pos:pos + n] = f[p:p + n]
+                out[pos:pos + seg.size] = seg
                 pos += n
             else:
-                pos += lz4mi.decompress_raw(f, p, n, out, pos, js_exact=js_exact)
-        out = out[:pos]
+                pos += block(p, n, out, pos)
     else:
+        # as the reference (:157-186): every block is decoded at the start of one 4 MiB workspace (whatever
+        # BD says, :41, :127), over what the block before it left there, the window passed as its dictionary
         parts, window = [], np.zeros(0, dtype=np.uint8)
+        ws = np.zeros(4194304, dtype=np.uint8)
         for p, n, stored in blocks:
             if stored:
                 piece = f[p:p + n].copy()
             else:
-                buf = np.concatenate([window, np.zeros(bmax, dtype=np.uint8)])
-                m = lz4mi.decompress_raw(f, p, n, buf, window.size, js_exact=js_exact)
-                piece = buf[window.size:window.size + m].copy()
+                piece = ws[:block(p, n, ws, 0, window if window.size else None)].copy()
             parts.append(piece)
             window = np.concatenate([window, piece])[-65536:]
         out = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)

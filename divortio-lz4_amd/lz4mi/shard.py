@@ -163,10 +163,13 @@ def frame_blocks(frame):
     """Walk a frame's blocks like the reference's decoder: returns (header_info, blocks)
     with blocks = [(payload_pos, size, stored)] in order and the position after the EndMark."""
     f = np.asarray(frame, dtype=np.uint8)
-    rd = lambda p: int(f[p]) | int(f[p + 1]) << 8 | int(f[p + 2]) << 16 | int(f[p + 3]) << 24 if p + 4 <= f.size else 0
+    # a byte past the frame's end reads as 0 (the reference's `undefined | 0`): a word the end cuts is
+    # assembled from the bytes that are there, as the device walk does (lz4mi_frame_index_kernel)
+    at = lambda p: int(f[p]) if p < f.size else 0
+    rd = lambda p: at(p) | at(p + 1) << 8 | at(p + 2) << 16 | at(p + 3) << 24
     if f.size < 4 or rd(0) != 0x184D2204:
         raise ValueError("LZ4: Invalid Magic Number")
-    flg, bd = int(f[4]), int(f[5])
+    flg, bd = at(4), at(5)
     pos = 6
     content_size = 0
     if flg & 0x08:

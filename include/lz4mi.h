@@ -312,6 +312,16 @@ int64_t lz4mi_host_decompress_block(const uint8_t* in, uint64_t in_total, int64_
  */
 int64_t lz4mi_host_decoded_size(const uint8_t* in, uint64_t in_total, int64_t in_off,
                                 int64_t in_size, int32_t* status);
+/*
+ * Where the reference's walk of a block stops reading: the position (in `in`) behind the last length
+ * or offset byte that decompressBlock reads for the block in[in_off .. +in_size). A well-formed block
+ * gives in_off + in_size or less. Above it the decoder has read bytes behind the block's end (an
+ * offset's second byte, a length's continuation bytes), which in the reference are the array's real
+ * bytes (zeros past in_total) but zeros for lz4mi_decompress_blocks, whose blocks end at in_len[b]:
+ * the frame layer decodes such a block of a damaged frame with lz4mi_host_decompress_block.
+ * Returns LZ4MI_ERR_ARG for negative positions.
+ */
+int64_t lz4mi_host_block_read_end(const uint8_t* in, uint64_t in_total, int64_t in_off, int64_t in_size);
 
 /*
  * Block index of a device-resident frame, for decoding its blocks on several devices

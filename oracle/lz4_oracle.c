@@ -217,7 +217,9 @@ int32_t orc_decompress_block(const uint8_t* in, uint64_t in_total, int64_t in_of
                              uint8_t* out, int64_t out_total, int64_t out_off,
                              const uint8_t* dict, int64_t dict_len, int32_t js_compat, int64_t* written) {
     src_t S = { in, (int64_t)in_total };
-    int64_t ip = in_off, iend = in_off + in_size, op = out_off;
+    /* inEnd = (inputOffset + inputSize) | 0 (:33): a declared size that carries the sum past 2^31 - 1
+     * wraps negative and the block decodes to nothing */
+    int64_t ip = in_off, iend = (int64_t)(int32_t)(uint32_t)(uint64_t)(in_off + in_size), op = out_off;
     if (written) *written = 0;
     while (ip < iend) {
         uint32_t token = getb(&S, ip++);
@@ -226,7 +228,9 @@ int32_t orc_decompress_block(const uint8_t* in, uint64_t in_total, int64_t in_of
         int64_t elit = op + lit;
         if (elit > out_total) return ORC_ERR_OUTPUT_TOO_SMALL;
         if (ip + lit > iend) return ORC_ERR_MALFORMED;
-        for (int64_t k = 0; k < lit; ++k) out[op + k] = getb(&S, ip + k);
+        /* 8..32 and below: byte stores, undefined reads as 0 (:86-120); above 32: output.set(input.subarray())
+         * (:82), which clips at the input's end and leaves the output bytes behind it as they were */
+        for (int64_t k = 0; k < lit; ++k) if (lit <= 32 || ip + k < S.total) out[op + k] = getb(&S, ip + k);
         op = elit; ip += lit;
         if (ip >= iend) break;
         uint32_t off = (uint32_t)getb(&S, ip) | ((uint32_t)getb(&S, ip + 1) << 8);
@@ -400,7 +404,7 @@ int32_t orc_decompress_frame(const uint8_t* data, int64_t len, const uint8_t* di
         memset(out, 0, (size_t)expected);
     } else {
         window = (uint8_t*)calloc(65536, 1);
-        ws = (uint8_t*)malloc(4194304);
+        ws = (uint8_t*)calloc(4194304, 1);     /* the reference's is module-level: bytes of earlier calls; here zeros */
         if (dict) {
             if (dict_len > 65536) { memcpy(window, dict + dict_len - 65536, 65536); wpos = 65536; }
             else { memcpy(window, dict, (size_t)dict_len); wpos = dict_len; }

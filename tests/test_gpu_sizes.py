@@ -186,6 +186,7 @@ def _check_measured_frame(f, data, has_checksum):
         if want not in (0, lz4mi.ERR_CHECKSUM):
             break
     assert want not in (0, lz4mi.ERR_CHECKSUM)
+    assert want == O.decompress_frame(t)[0]      # the reference's error for it, not only the host route's
     rep = {}
     assert _status_of(lambda: F.decompress_frame_device(torch.from_numpy(t.copy()).cuda(), report=rep)) == want
     assert rep == {"route": "host"}
