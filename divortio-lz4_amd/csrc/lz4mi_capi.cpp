@@ -18,45 +18,13 @@
 #include <sys/mman.h>
 
 #include "../../include/lz4mi.h"
-#include "lz4mi_decompress.h"
+#include "lz4mi_launch.h"
 
 #ifndef LZ4MI_SRC_HASH
 #define LZ4MI_SRC_HASH "unknown"
 #endif
 
-extern "C" hipError_t lz4mi_launch_decompress(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
-                                              const uint64_t*, const uint32_t*, const uint8_t*, uint32_t, uint32_t*,
-                                              int32_t*, uint32_t, int, uint32_t*, hipStream_t);
-extern "C" hipError_t lz4mi_launch_decompress_small(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
-                                                    const uint64_t*, const uint32_t*, const uint8_t*, uint32_t,
-                                                    uint32_t*, int32_t*, uint32_t, uint32_t, uint32_t, void*, int,
-                                                    int, hipStream_t);
-extern "C" size_t lz4mi_small_scratch_bytes(uint32_t, uint32_t, uint32_t);
-extern "C" hipError_t lz4mi_launch_decompress_linked(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
-                                                     const uint64_t*, const uint32_t*, const uint8_t*, uint32_t,
-                                                     uint32_t*, int32_t*, uint32_t, uint32_t, uint32_t, void*, int,
-                                                     int, int, hipStream_t);
-extern "C" size_t lz4mi_linked_scratch_bytes(uint32_t, uint32_t, uint32_t);
-extern "C" hipError_t lz4mi_launch_linked_fail(uint32_t*, int32_t*, uint32_t, uint32_t*, hipStream_t);
-extern "C" hipError_t lz4mi_launch_sizes(const uint8_t*, const uint64_t*, const uint32_t*, uint32_t*, int32_t*,
-                                         uint32_t, int, hipStream_t);
-extern "C" hipError_t lz4mi_launch_compress(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
-                                            const uint64_t*, uint32_t*, uint32_t, int32_t*, hipStream_t);
-extern "C" hipError_t lz4mi_launch_frame_pack(const uint8_t*, const uint64_t*, const uint32_t*, const uint8_t*,
-                                              const uint64_t*, const uint32_t*, uint8_t*, const uint64_t*, uint32_t,
-                                              uint64_t*, uint64_t*, uint32_t*, hipStream_t);
-extern "C" hipError_t lz4mi_launch_compress_chain(const uint8_t*, uint64_t, int32_t, int32_t, int32_t, int32_t*,
-                                                  uint8_t*, const uint64_t*, uint32_t*, uint32_t, hipStream_t);
-extern "C" hipError_t lz4mi_launch_xxh32(const uint8_t*, const uint64_t*, const uint32_t*, uint32_t, uint32_t*,
-                                         uint32_t, int, uint8_t*, const uint64_t*, hipStream_t);
-extern "C" hipError_t lz4mi_launch_generate(uint8_t*, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
-extern "C" hipError_t lz4mi_launch_frame_scan(const uint8_t*, uint64_t, uint32_t, uint64_t*, uint32_t*, uint64_t*,
-                                              uint32_t*, uint64_t*, uint32_t*, uint64_t*, uint32_t*, uint32_t*,
-                                              int64_t*, hipStream_t);
-extern "C" hipError_t lz4mi_launch_frame_index(const uint8_t*, uint64_t, uint32_t, uint64_t*, uint32_t*, int64_t*,
-                                               hipStream_t);
-extern "C" hipError_t lz4mi_launch_frame_stored(const uint8_t*, uint64_t, const uint64_t*, const uint32_t*,
-                                                const uint64_t*, uint8_t*, uint64_t, uint32_t, hipStream_t);
+using lz4mi::Batch;
 
 namespace {
 
@@ -75,11 +43,6 @@ struct Scratch {
         if (e == hipSuccess) cap = want;
         return e;
     }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
@@ -97,13 +60,6 @@ struct StreamCtx {
     Scratch scan;         // frame_decompress: block lists of the device frame walk
     Scratch order;        // batch decode: the blocks' dispatch order (lz4mi_block_order_kernel)
     Scratch small;        // small-batch decode: exported sequences and output pointers (lz4mi_expand.hip)
-    void release() {
-        tables.release();
-        frame_meta.release();
-        scan.release();
-        order.release();
-        small.release();
-    }
 };
 
 struct Ctx {
@@ -113,7 +69,6 @@ struct Ctx {
     std::mutex mu;                // serialises the host-pointer entry points (their staging is shared)
     std::mutex streams_mu;
     std::vector<std::unique_ptr<StreamCtx>> streams;
-    Scratch stats;
 };
 
 Ctx g_ctx;
@@ -192,9 +147,31 @@ size_t small_scratch_cap() {
     }();
     return n;
 }
-int small_reparse_hook() {   // (test hook, read per call: LZ4MI_SMALL_REPARSE forces re-parses, tests/test_gpu_small.py)
-    const char* e = std::getenv("LZ4MI_SMALL_REPARSE");
-    return e ? std::atoi(e) : 0;
+// Test hooks, read per call. LZ4MI_SMALL_REPARSE forces re-parses (tests/test_gpu_small.py);
+// LZ4MI_TEST_SCRATCH_EXTRA_MB asks for that much more scratch, so that the allocation really fails
+// (tests/test_gpu_small.py::test_small_batch_scratch_allocation_failure); LZ4MI_LINKED_WINDOW
+// bounds a linked window's blocks (0: no bound).
+unsigned long long hook(const char* name) {
+    const char* e = std::getenv(name);
+    return e ? std::strtoull(e, nullptr, 10) : 0;
+}
+int small_reparse_hook() { return (int)hook("LZ4MI_SMALL_REPARSE"); }
+size_t scratch_extra_hook() { return (size_t)hook("LZ4MI_TEST_SCRATCH_EXTRA_MB") << 20; }
+uint32_t linked_window_hook() { return (uint32_t)hook("LZ4MI_LINKED_WINDOW"); }
+
+// The export limits of a small-path or linked pass: the batch's largest compressed block rounded
+// up to 64 KiB, its largest capacity to a power of two (lz4mi_launch_expand tiles it), both at
+// most the path's limits; 0 = unknown (device pointers): the path's limits.
+struct XLimits {
+    uint32_t xi, xo;
+};
+XLimits export_limits(uint32_t in_max, uint32_t out_max) {
+    constexpr uint32_t kGrain = 64u << 10;
+    const uint32_t xi = in_max ? std::min(kSmallInMax, (in_max + kGrain - 1) / kGrain * kGrain) : kSmallInMax;
+    uint32_t xo = kGrain;
+    while (xo < out_max && xo < kSmallOutMax) xo <<= 1;
+    if (!out_max) xo = kSmallOutMax;
+    return {xi, xo};
 }
 
 // `order`: scratch of nblocks words for the dispatch order, owned by the caller's lock
@@ -219,27 +196,16 @@ extern "C" __attribute__((visibility("hidden"))) void lz4mi_advise_output(void* 
 
 namespace {
 
-hipError_t decode_launch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
-                         const uint64_t* out_off, const uint32_t* out_cap, const uint8_t* dict, uint32_t dict_len,
-                         uint32_t* out_len, int32_t* status, uint32_t nblocks, int mode, hipStream_t s,
-                         Scratch* order, Scratch* small = nullptr, uint32_t in_max = 0, uint32_t out_max = 0) {
+hipError_t decode_launch(const Batch& b, int mode, hipStream_t s, Scratch* order, Scratch* small = nullptr,
+                         uint32_t in_max = 0, uint32_t out_max = 0) {
+    const uint32_t nblocks = b.nblocks;
     if (small && (mode == 0 || mode == 2) && nblocks <= small_blocks()) {
-        // (the output limit is a power of two: lz4mi_launch_expand tiles it)
-        constexpr uint32_t kGrain = 64u << 10;
-        const uint32_t xi = in_max ? std::min(kSmallInMax, (in_max + kGrain - 1) / kGrain * kGrain) : kSmallInMax;
-        uint32_t xo = kGrain;
-        while (xo < out_max && xo < kSmallOutMax) xo <<= 1;
-        if (!out_max) xo = kSmallOutMax;
-        const size_t need = lz4mi_small_scratch_bytes(nblocks, xi, xo);
+        const XLimits x = export_limits(in_max, out_max);
+        const size_t need = lz4mi_small_scratch_bytes(nblocks, x.xi, x.xo);
+        // (the cap bounds `need` here and the real allocation in linked_launch: the two differ; ADVICE's item on it is open)
         if (need <= small_scratch_cap()) {
-            // (test hook, read per call: LZ4MI_TEST_SCRATCH_EXTRA_MB asks for that much more, so that the
-            // allocation really fails -- tests/test_gpu_small.py::test_small_batch_scratch_allocation_failure)
-            const char* xe = std::getenv("LZ4MI_TEST_SCRATCH_EXTRA_MB");
-            const size_t extra = xe ? (size_t)std::strtoull(xe, nullptr, 10) << 20 : 0;
-            if (small->ensure(need + extra, s) == hipSuccess)
-                return lz4mi_launch_decompress_small(in, in_off, in_len, out, out_off, out_cap, dict, dict_len,
-                                                     out_len, status, nblocks, xi, xo, small->p, small_reparse_hook(),
-                                                     mode == 2 ? 1 : 0, s);
+            if (small->ensure(need + scratch_extra_hook(), s) == hipSuccess)
+                return lz4mi_launch_decompress_small(b, x.xi, x.xo, small->p, small_reparse_hook(), mode == 2 ? 1 : 0, s);
             (void)hipGetLastError();   // the failed allocation is not this call's error: the batch kernel runs
         }
     }
@@ -248,8 +214,7 @@ hipError_t decode_launch(const uint8_t* in, const uint64_t* in_off, const uint32
         if (order->ensure((size_t)nblocks * 4, s) == hipSuccess) ord = order->as<uint32_t>();
         else (void)hipGetLastError();   // index order instead
     }
-    return lz4mi_launch_decompress(in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status,
-                                   nblocks, mode, ord, s);
+    return lz4mi_launch_decompress(b, mode, ord, s);
 }
 
 // LZ4MI_LINKED (include/lz4mi.h; kernels: lz4mi_expand.hip "linked mode"): the batch is cut into
@@ -267,24 +232,17 @@ hipError_t decode_launch(const uint8_t* in, const uint64_t* in_off, const uint32
 // export limits); h_*: the host's copies of the arrays (nullptr with device pointers).
 uint64_t g_linked_stats[4];   // the last linked call: windows, scratch bytes, x_in_max, x_out_max (lz4mi_debug_linked_stats)
 
-hipError_t linked_launch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
-                         const uint64_t* out_off, const uint32_t* out_cap, const uint8_t* dict, uint32_t dict_len,
-                         uint32_t* out_len, int32_t* status, uint32_t nblocks, int fw, hipStream_t s, Scratch* small,
-                         uint32_t in_max, uint32_t out_max, const uint64_t* h_in_off, const uint32_t* h_in_len,
-                         const uint64_t* h_out_off, const uint32_t* h_out_cap) {
-    constexpr uint32_t kGrain = 64u << 10;
-    const uint32_t xi = in_max ? std::min(kSmallInMax, (in_max + kGrain - 1) / kGrain * kGrain) : kSmallInMax;
-    uint32_t xo = kGrain;
-    while (xo < out_max && xo < kSmallOutMax) xo <<= 1;
-    if (!out_max) xo = kSmallOutMax;
+hipError_t linked_launch(const Batch& b, int fw, hipStream_t s, Scratch* small, uint32_t in_max, uint32_t out_max,
+                         const uint64_t* h_in_off = nullptr, const uint32_t* h_in_len = nullptr,
+                         const uint64_t* h_out_off = nullptr, const uint32_t* h_out_cap = nullptr) {
+    const XLimits x = export_limits(in_max, out_max);
+    const uint32_t nblocks = b.nblocks, xi = x.xi, xo = x.xo;
     auto alloc_of = [&](uint32_t nb) {
         const size_t need = lz4mi_linked_scratch_bytes(nb, xi, xo);
         return std::max<size_t>(need + need / 4, 1 << 20);
     };
     uint32_t wmax = std::min<uint32_t>(nblocks, ((1u << 30) - 65536u) / xo);
-    const char* we = std::getenv("LZ4MI_LINKED_WINDOW");
-    const uint32_t hook = we ? (uint32_t)std::strtoul(we, nullptr, 10) : 0u;
-    if (hook) wmax = std::min(wmax, hook);
+    if (const uint32_t hook = linked_window_hook()) wmax = std::min(wmax, hook);
     uint32_t lo = 0, hi = wmax;
     while (lo < hi) {   // the most blocks whose allocation stays within the cap
         const uint32_t mid = lo + (hi - lo + 1) / 2;
@@ -293,9 +251,7 @@ hipError_t linked_launch(const uint8_t* in, const uint64_t* in_off, const uint32
     }
     wmax = lo;
     if (wmax) {
-        const char* xe = std::getenv("LZ4MI_TEST_SCRATCH_EXTRA_MB");
-        const size_t extra = xe ? (size_t)std::strtoull(xe, nullptr, 10) << 20 : 0;
-        if (small->ensure(lz4mi_linked_scratch_bytes(wmax, xi, xo) + extra, s) != hipSuccess) {
+        if (small->ensure(lz4mi_linked_scratch_bytes(wmax, xi, xo) + scratch_extra_hook(), s) != hipSuccess) {
             (void)hipGetLastError();
             wmax = 0;
         }
@@ -308,12 +264,11 @@ hipError_t linked_launch(const uint8_t* in, const uint64_t* in_off, const uint32
     g_linked_stats[2] = xi;
     g_linked_stats[3] = xo;
     if (!wmax) {
-        for (uint32_t b = 0; b < nblocks; ++b) {
-            e = lz4mi_launch_decompress(in, in_off + b, in_len + b, out, out_off + b, out_cap + b, dict, dict_len,
-                                        out_len + b, status + b, 1, fw ? 4 : 0, nullptr, s);
+        for (uint32_t k = 0; k < nblocks; ++k) {
+            e = lz4mi_launch_decompress(b.slice(k, 1), fw ? 4 : 0, nullptr, s);
             if (e != hipSuccess) return e;
         }
-        return lz4mi_launch_linked_fail(out_len, status, nblocks, small->as<uint32_t>(), s);
+        return lz4mi_launch_linked_fail(b.out_len, b.status, nblocks, small->as<uint32_t>(), s);
     }
     for (uint32_t w0 = 0; w0 < nblocks;) {
         uint32_t nb = std::min(wmax, nblocks - w0);
@@ -329,9 +284,7 @@ hipError_t linked_launch(const uint8_t* in, const uint64_t* in_off, const uint32
             }
             nb = k;
         }
-        e = lz4mi_launch_decompress_linked(in, in_off + w0, in_len + w0, out, out_off + w0, out_cap + w0, dict, dict_len,
-                                           out_len + w0, status + w0, nb, xi, xo, small->p, small_reparse_hook(), fw,
-                                           w0 ? 1 : 0, s);
+        e = lz4mi_launch_decompress_linked(b.slice(w0, nb), xi, xo, small->p, small_reparse_hook(), fw, w0 ? 1 : 0, s);
         if (e != hipSuccess) return e;
         ++g_linked_stats[0];
         w0 += nb;
@@ -340,6 +293,50 @@ hipError_t linked_launch(const uint8_t* in, const uint64_t* in_off, const uint32
 }
 
 inline uint64_t round16(uint64_t n) { return (n + 15u) & ~15ull; }
+
+// Input side of the synchronous host-pointer entry points (the caller holds g_ctx.mu), in two
+// steps so that an entry point can queue copies of its own between them. copy(): the blocks'
+// bytes packed at 16-byte-aligned offsets into g_ctx.in, and g_ctx.meta laid out as in_off, n64
+// more arrays of nblocks u64 (`more64`), in_len, n32 more arrays of nblocks u32 (`more32`) -- the
+// entry point's own; frame_words: a stored frame word (bit 31) stages no bytes. upload(): the
+// offsets, the caller's device-side output offsets if it has any (into more64), the lengths.
+struct StagedIn {
+    std::vector<uint64_t> h_in_off;   // the host's copy of in_off
+    const uint32_t* h_in_len;
+    uint32_t nblocks;
+    uint8_t* in;
+    uint64_t *in_off, *more64;
+    uint32_t *in_len, *more32;
+
+    int32_t copy(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len, uint32_t n, bool frame_words,
+                 uint32_t n64, uint32_t n32, hipStream_t s) {
+        auto bytes = [&](uint32_t b) -> uint64_t { return (frame_words && (src_len[b] & 0x80000000u)) ? 0 : src_len[b]; };
+        h_in_len = src_len;
+        nblocks = n;
+        h_in_off.resize(n);
+        uint64_t total = 0;
+        for (uint32_t b = 0; b < n; ++b) {
+            h_in_off[b] = total;
+            total += round16(bytes(b));
+        }
+        LZ4MI_TRY(g_ctx.in.ensure(total + 64, s));
+        LZ4MI_TRY(g_ctx.meta.ensure((size_t)n * (8 + 8 * n64 + 4 + 4 * n32) + 64, s));
+        in = g_ctx.in.as<uint8_t>();
+        in_off = g_ctx.meta.as<uint64_t>();
+        more64 = in_off + n;
+        in_len = (uint32_t*)(more64 + (size_t)n64 * n);
+        more32 = in_len + n;
+        for (uint32_t b = 0; b < n; ++b)
+            if (bytes(b)) LZ4MI_TRY(hipMemcpyAsync(in + h_in_off[b], src + src_off[b], bytes(b), hipMemcpyHostToDevice, s));
+        return LZ4MI_OK;
+    }
+    int32_t upload(const uint64_t* h_out_off, hipStream_t s) {
+        LZ4MI_TRY(hipMemcpyAsync(in_off, h_in_off.data(), 8ull * nblocks, hipMemcpyHostToDevice, s));
+        if (h_out_off) LZ4MI_TRY(hipMemcpyAsync(more64, h_out_off, 8ull * nblocks, hipMemcpyHostToDevice, s));
+        LZ4MI_TRY(hipMemcpyAsync(in_len, h_in_len, 4ull * nblocks, hipMemcpyHostToDevice, s));
+        return LZ4MI_OK;
+    }
+};
 
 // ---- host XXH32 (reference variant by default, see lz4mi_xxh32.hip) -------
 constexpr uint32_t P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
@@ -532,13 +529,9 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
         hipStream_t s = pick_stream(stream);
         StreamCtx* c = stream_ctx(s);
         std::lock_guard<std::mutex> sl(c->mu);
-        if (linked) {
-            LZ4MI_TRY(linked_launch(in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks,
-                                    (mode & 4) ? 1 : 0, s, &c->small, 0, 0, nullptr, nullptr, nullptr, nullptr));
-            return LZ4MI_OK;
-        }
-        LZ4MI_TRY(decode_launch(in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks,
-                                mode, s, &c->order, &c->small));
+        const Batch batch{in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks};
+        if (linked) LZ4MI_TRY(linked_launch(batch, (mode & 4) ? 1 : 0, s, &c->small, 0, 0));
+        else LZ4MI_TRY(decode_launch(batch, mode, s, &c->order, &c->small));
         return LZ4MI_OK;
     }
     if (!in || !out || !in_off || !in_len || !out_off || !out_cap || !out_len || !status) return LZ4MI_ERR_ARG;
@@ -554,60 +547,42 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
     // Pack the compressed blocks; stage the output image [lo - hist, hi) so
     // back-references into bytes preceding a block (reference semantics:
     // positions are absolute in `out`) see the caller's bytes.
-    uint64_t in_total = 0, lo = UINT64_MAX, hi = 0;
+    uint64_t lo = UINT64_MAX, hi = 0;
     for (uint32_t b = 0; b < nblocks; ++b) {
-        in_total += round16(in_len[b]);
         lo = std::min<uint64_t>(lo, out_off[b]);
         hi = std::max<uint64_t>(hi, out_off[b] + out_cap[b]);
     }
     uint64_t hist = std::min<uint64_t>(lo, 65536);
     uint64_t base = lo - hist, img = hi - base;
     lz4mi_advise_output(out + lo, hi - lo);
-    std::vector<uint64_t> d_in_off(nblocks), d_out_off(nblocks);
-    uint64_t pos = 0;
-    for (uint32_t b = 0; b < nblocks; ++b) {
-        d_in_off[b] = pos;
-        pos += round16(in_len[b]);
-        d_out_off[b] = out_off[b] - base;
-    }
+    std::vector<uint64_t> d_out_off(nblocks);
+    for (uint32_t b = 0; b < nblocks; ++b) d_out_off[b] = out_off[b] - base;
     // Dictionary bytes are only reachable when the image starts at out[0].
     uint32_t dlen = (base == 0 && dict) ? dict_len : 0;
-    LZ4MI_TRY(g_ctx.in.ensure(in_total + 64, s));
     LZ4MI_TRY(g_ctx.out.ensure(img + 64, s));
     LZ4MI_TRY(g_ctx.aux.ensure((size_t)dlen + 64, s));
-    const size_t meta_bytes = (size_t)nblocks * (8 + 4 + 8 + 4 + 4 + 4);
-    LZ4MI_TRY(g_ctx.meta.ensure(meta_bytes + 64, s));
-    uint8_t* m = g_ctx.meta.as<uint8_t>();
-    uint64_t* m_in_off = (uint64_t*)m;
-    uint64_t* m_out_off = m_in_off + nblocks;
-    uint32_t* m_in_len = (uint32_t*)(m_out_off + nblocks);
-    uint32_t* m_out_cap = m_in_len + nblocks;
+    StagedIn st;   // meta: in_off, out_off, in_len, out_cap, out_len, status
+    if (int32_t e = st.copy(in, in_off, in_len, nblocks, false, 1, 3, s)) return e;
+    uint32_t* m_out_cap = st.more32;
     uint32_t* m_out_len = m_out_cap + nblocks;
     int32_t* m_status = (int32_t*)(m_out_len + nblocks);
-    for (uint32_t b = 0; b < nblocks; ++b)
-        LZ4MI_TRY(hipMemcpyAsync(g_ctx.in.as<uint8_t>() + d_in_off[b], in + in_off[b], in_len[b],
-                                 hipMemcpyHostToDevice, s));
     // js-compat may rewrite bytes anywhere before a match and its result is
     // copied back whole: stage the whole image so untouched bytes survive.
     // (linked: a later block may read the caller's bytes in a gap or in the unused tail of a slot)
     const uint64_t up = (js || linked) ? img : hist;
     if (up) LZ4MI_TRY(hipMemcpyAsync(g_ctx.out.p, out + base, up, hipMemcpyHostToDevice, s));
     if (dlen) LZ4MI_TRY(hipMemcpyAsync(g_ctx.aux.p, dict, dlen, hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_in_off, d_in_off.data(), 8ull * nblocks, hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_out_off, d_out_off.data(), 8ull * nblocks, hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_in_len, in_len, 4ull * nblocks, hipMemcpyHostToDevice, s));
+    if (int32_t e = st.upload(d_out_off.data(), s)) return e;
     LZ4MI_TRY(hipMemcpyAsync(m_out_cap, out_cap, 4ull * nblocks, hipMemcpyHostToDevice, s));
     const uint32_t in_max = *std::max_element(in_len, in_len + nblocks);
     const uint32_t out_max = *std::max_element(out_cap, out_cap + nblocks);
+    const Batch batch{st.in, st.in_off, st.in_len, g_ctx.out.as<uint8_t>(), st.more64, m_out_cap,
+                  dlen ? g_ctx.aux.as<uint8_t>() : nullptr, dlen, m_out_len, m_status, nblocks};
     if (linked)
-        LZ4MI_TRY(linked_launch(g_ctx.in.as<uint8_t>(), m_in_off, m_in_len, g_ctx.out.as<uint8_t>(), m_out_off, m_out_cap,
-                                dlen ? g_ctx.aux.as<uint8_t>() : nullptr, dlen, m_out_len, m_status, nblocks, 0, s,
-                                &g_ctx.small, std::max(in_max, 1u), std::max(out_max, 1u), d_in_off.data(), in_len,
-                                d_out_off.data(), out_cap));
+        LZ4MI_TRY(linked_launch(batch, 0, s, &g_ctx.small, std::max(in_max, 1u), std::max(out_max, 1u), st.h_in_off.data(),
+                                in_len, d_out_off.data(), out_cap));
     else
-    LZ4MI_TRY(decode_launch(g_ctx.in.as<uint8_t>(), m_in_off, m_in_len, g_ctx.out.as<uint8_t>(), m_out_off, m_out_cap,
-                            dlen ? g_ctx.aux.as<uint8_t>() : nullptr, dlen, m_out_len, m_status, nblocks, mode, s,
-                            &g_ctx.order, &g_ctx.small, std::max(in_max, 1u), std::max(out_max, 1u)));
+        LZ4MI_TRY(decode_launch(batch, mode, s, &g_ctx.order, &g_ctx.small, std::max(in_max, 1u), std::max(out_max, 1u)));
     LZ4MI_TRY(hipMemcpyAsync(out_len, m_out_len, 4ull * nblocks, hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipMemcpyAsync(status, m_status, 4ull * nblocks, hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipStreamSynchronize(s));
@@ -636,6 +611,19 @@ int lz4mi_debug_linked_stats(unsigned long long* out) {
     return 0;
 }
 
+// The scratch layout of a small-path pass or linked window (tests/test_capi_cpu.py): offset and bytes of the
+// head, xseq, xcnt, xfirst, xrec, ptr, flags, best, redo and done, then the total: 21 values.
+int lz4mi_debug_layout(uint32_t nblocks, uint32_t x_in_max, uint32_t x_out_max, int linked, unsigned long long* out) {
+    const lz4mi::XLayout L = lz4mi::x_layout(nblocks, x_in_max, x_out_max, linked != 0);
+    const lz4mi::XRegion* r[10] = {&L.head, &L.xseq, &L.xcnt, &L.xfirst, &L.xrec, &L.ptr, &L.flags, &L.best, &L.redo, &L.done};
+    for (int k = 0; k < 10; ++k) {
+        out[2 * k] = r[k]->off;
+        out[2 * k + 1] = r[k]->bytes;
+    }
+    out[20] = L.total;
+    return 0;
+}
+
 int32_t lz4mi_decoded_sizes(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t* out_len,
                             int32_t* status, uint32_t nblocks, uint32_t flags, void* stream) {
     if (flags & ~(LZ4MI_DEVICE_PTRS | LZ4MI_FRAME_WORDS)) return LZ4MI_ERR_ARG;
@@ -650,26 +638,12 @@ int32_t lz4mi_decoded_sizes(const uint8_t* in, const uint64_t* in_off, const uin
     }
     std::lock_guard<std::mutex> lk(g_ctx.mu);
     hipStream_t s = g_ctx.stream;
-    auto bytes = [&](uint32_t b) -> uint64_t { return (fw && (in_len[b] & 0x80000000u)) ? 0 : in_len[b]; };
-    std::vector<uint64_t> d_in_off(nblocks);
-    uint64_t in_total = 0;
-    for (uint32_t b = 0; b < nblocks; ++b) {
-        d_in_off[b] = in_total;
-        in_total += round16(bytes(b));
-    }
-    LZ4MI_TRY(g_ctx.in.ensure(in_total + 64, s));
-    LZ4MI_TRY(g_ctx.meta.ensure((size_t)nblocks * (8 + 4 + 4 + 4) + 64, s));
-    uint64_t* m_in_off = g_ctx.meta.as<uint64_t>();
-    uint32_t* m_in_len = (uint32_t*)(m_in_off + nblocks);
-    uint32_t* m_out_len = m_in_len + nblocks;
+    StagedIn st;   // meta: in_off, in_len, out_len, status
+    if (int32_t e = st.copy(in, in_off, in_len, nblocks, fw != 0, 0, 2, s)) return e;
+    if (int32_t e = st.upload(nullptr, s)) return e;
+    uint32_t* m_out_len = st.more32;
     int32_t* m_status = (int32_t*)(m_out_len + nblocks);
-    for (uint32_t b = 0; b < nblocks; ++b)
-        if (bytes(b))
-            LZ4MI_TRY(hipMemcpyAsync(g_ctx.in.as<uint8_t>() + d_in_off[b], in + in_off[b], bytes(b),
-                                     hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_in_off, d_in_off.data(), 8ull * nblocks, hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_in_len, in_len, 4ull * nblocks, hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(lz4mi_launch_sizes(g_ctx.in.as<uint8_t>(), m_in_off, m_in_len, m_out_len, m_status, nblocks, fw, s));
+    LZ4MI_TRY(lz4mi_launch_sizes(st.in, st.in_off, st.in_len, m_out_len, m_status, nblocks, fw, s));
     LZ4MI_TRY(hipMemcpyAsync(out_len, m_out_len, 4ull * nblocks, hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipMemcpyAsync(status, m_status, 4ull * nblocks, hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipStreamSynchronize(s));
@@ -696,32 +670,22 @@ int32_t lz4mi_compress_blocks(const uint8_t* in, const uint64_t* in_off, const u
         if (in_len[b] > LZ4MI_MAX_BLOCK) return LZ4MI_ERR_ARG;
     std::lock_guard<std::mutex> lk(g_ctx.mu);
     hipStream_t s = g_ctx.stream;
-    std::vector<uint64_t> d_in_off(nblocks), d_out_off(nblocks);
-    uint64_t ipos = 0, opos = 0;
+    std::vector<uint64_t> d_out_off(nblocks);
+    uint64_t opos = 0;
     for (uint32_t b = 0; b < nblocks; ++b) {
-        d_in_off[b] = ipos;
-        ipos += round16(in_len[b]);
         d_out_off[b] = opos;
         opos += round16(lz4mi_compress_bound(in_len[b]));
     }
-    LZ4MI_TRY(g_ctx.in.ensure(ipos + 64, s));
+    StagedIn st;   // meta: in_off, out_off, in_len, out_len
     LZ4MI_TRY(g_ctx.out.ensure(opos + 64, s));
-    LZ4MI_TRY(g_ctx.meta.ensure((size_t)nblocks * 24 + 64, s));
-    uint64_t* m_in_off = g_ctx.meta.as<uint64_t>();
-    uint64_t* m_out_off = m_in_off + nblocks;
-    uint32_t* m_in_len = (uint32_t*)(m_out_off + nblocks);
-    uint32_t* m_out_len = m_in_len + nblocks;
-    for (uint32_t b = 0; b < nblocks; ++b)
-        LZ4MI_TRY(hipMemcpyAsync(g_ctx.in.as<uint8_t>() + d_in_off[b], in + in_off[b], in_len[b],
-                                 hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_in_off, d_in_off.data(), 8ull * nblocks, hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_out_off, d_out_off.data(), 8ull * nblocks, hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_in_len, in_len, 4ull * nblocks, hipMemcpyHostToDevice, s));
+    if (int32_t e = st.copy(in, in_off, in_len, nblocks, false, 1, 1, s)) return e;
+    if (int32_t e = st.upload(d_out_off.data(), s)) return e;
+    uint32_t* m_out_len = st.more32;
     StreamCtx* c = stream_ctx(s);
     std::unique_lock<std::mutex> sl(c->mu);
     LZ4MI_TRY(c->tables.ensure((size_t)nblocks * 16384 * sizeof(int32_t), s));
-    LZ4MI_TRY(lz4mi_launch_compress(g_ctx.in.as<uint8_t>(), m_in_off, m_in_len, g_ctx.out.as<uint8_t>(), m_out_off,
-                                    m_out_len, nblocks, c->tables.as<int32_t>(), s));
+    LZ4MI_TRY(lz4mi_launch_compress(st.in, st.in_off, st.in_len, g_ctx.out.as<uint8_t>(), st.more64, m_out_len, nblocks,
+                                    c->tables.as<int32_t>(), s));
     LZ4MI_TRY(hipMemcpyAsync(out_len, m_out_len, 4ull * nblocks, hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipStreamSynchronize(s));
     uint64_t olo = UINT64_MAX, ohi = 0;
@@ -830,19 +794,11 @@ int32_t lz4mi_xxh32_blocks(const uint8_t* in, const uint64_t* off, const uint32_
     if (!in || !off || !len || !hashes) return LZ4MI_ERR_ARG;
     std::lock_guard<std::mutex> lk(g_ctx.mu);
     hipStream_t s = g_ctx.stream;
-    std::vector<uint64_t> d_off(nblocks);
-    uint64_t pos = 0;
-    for (uint32_t b = 0; b < nblocks; ++b) { d_off[b] = pos; pos += round16(len[b]); }
-    LZ4MI_TRY(g_ctx.in.ensure(pos + 64, s));
-    LZ4MI_TRY(g_ctx.meta.ensure((size_t)nblocks * 16 + 64, s));
-    uint64_t* m_off = g_ctx.meta.as<uint64_t>();
-    uint32_t* m_len = (uint32_t*)(m_off + nblocks);
-    uint32_t* m_h = m_len + nblocks;
-    for (uint32_t b = 0; b < nblocks; ++b)
-        LZ4MI_TRY(hipMemcpyAsync(g_ctx.in.as<uint8_t>() + d_off[b], in + off[b], len[b], hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_off, d_off.data(), 8ull * nblocks, hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(hipMemcpyAsync(m_len, len, 4ull * nblocks, hipMemcpyHostToDevice, s));
-    LZ4MI_TRY(lz4mi_launch_xxh32(g_ctx.in.as<uint8_t>(), m_off, m_len, seed, m_h, nblocks, stdv, nullptr, nullptr, s));
+    StagedIn st;   // meta: off, len, hashes
+    if (int32_t e = st.copy(in, off, len, nblocks, false, 0, 1, s)) return e;
+    if (int32_t e = st.upload(nullptr, s)) return e;
+    uint32_t* m_h = st.more32;
+    LZ4MI_TRY(lz4mi_launch_xxh32(st.in, st.in_off, st.in_len, seed, m_h, nblocks, stdv, nullptr, nullptr, s));
     LZ4MI_TRY(hipMemcpyAsync(hashes, m_h, 4ull * nblocks, hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipStreamSynchronize(s));
     return LZ4MI_OK;
@@ -945,12 +901,9 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     // (LZ4MI_LINKED: after the stored copies, the compressed blocks in one linked call -- their slots ascend in
     // frame order, the stored blocks lie in the gaps; sized for the frame's block_max, which a compressed
     // block of the reference's layout does not exceed: one that does is refused and decoded alone below)
-    if (nc && linked)
-        LZ4MI_TRY(linked_launch(frame, c_in_off, c_in_len, out, c_out_off, c_out_cap, nullptr, 0, d_out_len, d_status, nc,
-                                0, s, &c->small, (uint32_t)bmax, (uint32_t)bmax, nullptr, nullptr, nullptr, nullptr));
-    else
-    if (nc) LZ4MI_TRY(decode_launch(frame, c_in_off, c_in_len, out, c_out_off, c_out_cap, nullptr, 0, d_out_len,
-                                    d_status, nc, mode, s, &c->order));
+    const Batch cb{frame, c_in_off, c_in_len, out, c_out_off, c_out_cap, nullptr, 0, d_out_len, d_status, nc};
+    if (nc && linked) LZ4MI_TRY(linked_launch(cb, 0, s, &c->small, (uint32_t)bmax, (uint32_t)bmax));
+    else if (nc) LZ4MI_TRY(decode_launch(cb, mode, s, &c->order));
     std::vector<uint32_t> olen(nc), cap(nc), cidx(nc), slen(ns), sidx(ns);
     std::vector<int32_t> stat(nc);
     std::vector<uint64_t> soff(ns), ooff(nc), ioff(nc);
@@ -972,8 +925,7 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     // unless a block failed or was refused -- the blocks from there on are resumed here)
     for (uint32_t k = 0; k < nc; ++k) {
         if (stat[k] != LZ4MI_ERR_CROSS_BLOCK && !(linked && stat[k] == LZ4MI_ERR_ARG)) continue;
-        LZ4MI_TRY(decode_launch(frame, c_in_off + k, c_in_len + k, out, c_out_off + k, c_out_cap + k, nullptr, 0,
-                                d_out_len + k, d_status + k, 1, mode, s, nullptr));
+        LZ4MI_TRY(decode_launch(cb.slice(k, 1), mode, s, nullptr));
         LZ4MI_TRY(hipMemcpyAsync(&olen[k], d_out_len + k, 4, hipMemcpyDeviceToHost, s));
         LZ4MI_TRY(hipMemcpyAsync(&stat[k], d_status + k, 4, hipMemcpyDeviceToHost, s));
         LZ4MI_TRY(hipStreamSynchronize(s));

@@ -15,6 +15,7 @@
 //                                table (LZ4.compressRaw): one wave, the table, the
 //                                source window and the output ring in LDS.
 #include "lz4mi_common.h"
+#include "lz4mi_launch.h"
 
 #include <cstdlib>
 

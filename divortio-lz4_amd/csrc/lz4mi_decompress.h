@@ -78,5 +78,3 @@ __host__ __device__ constexpr uint32_t seg_block_capacity(uint32_t x_in_max) { r
 constexpr uint32_t kNotExported = 0xFFFFFFFFu;
 
 }  // namespace lz4mi
-
-extern "C" hipError_t lz4mi_launch_decompress_serial(const lz4mi::DecArgs& a, hipStream_t stream);

@@ -49,6 +49,7 @@
 #include "../../include/lz4mi.h"
 #include "lz4mi_common.h"
 #include "lz4mi_decompress.h"
+#include "lz4mi_launch.h"
 
 #ifndef LZ4MI_LL_ADAPT
 #define LZ4MI_LL_ADAPT 127   // long literal runs: s_sleep argument after every 4 KiB step while blocks with a
@@ -2159,118 +2160,109 @@ extern "C" int lz4mi_debug_timeline(unsigned long long* t, unsigned int* id, uns
 }
 #endif
 
-extern "C" hipError_t lz4mi_launch_decompress(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                              uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                              const uint8_t* dict, uint32_t dict_len, uint32_t* out_len,
-                                              int32_t* status, uint32_t nblocks, int mode, uint32_t* order,
-                                              hipStream_t stream) {
+using lz4mi::Batch;
+using lz4mi::DecArgs;
+using lz4mi::XLayout;
+
+// The kernels' arguments for the blocks of `b` (the export fields: parse_exported)
+static DecArgs dec_args(const Batch& b, int isolate, int f1check) {
+    return DecArgs{b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.dict, b.dict_len, b.out_len, b.status,
+                   b.nblocks, isolate, f1check};
+}
+
+extern "C" hipError_t lz4mi_launch_decompress(const Batch& b, int mode, uint32_t* order, hipStream_t stream) {
     // mode 0: LZ4 spec; 1: reference-exact serial kernel; 2: spec kernel with the in-chunk
     // reference-exact fix-up of every chunk a double-copy-tail rewrite changes (f1_fixup).
     // order: nblocks words of scratch for the dispatch order (nullptr: index order)
     // mode bit 2 (4): in_len holds frame size words (LZ4MI_FRAME_WORDS)
     const int fw = (mode & 4) ? 1 : 0;
     mode &= 3;
-    lz4mi::DecArgs a{in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks,
-                     nblocks > 1 ? 1 : 0, mode == 2 ? 1 : 0};
+    const uint32_t nblocks = b.nblocks;
+    DecArgs a = dec_args(b, nblocks > 1 ? 1 : 0, mode == 2 ? 1 : 0);
     a.frame_words = fw;
     if (nblocks == 0) return hipSuccess;
     if (mode == 1) return lz4mi_launch_decompress_serial(a, stream);
     if (LZ4MI_ORDER && order && nblocks > 1 && nblocks <= lz4mi::kOrderMax) {
-        hipLaunchKernelGGL(lz4mi::lz4mi_block_order_kernel, dim3(1), dim3(1024), 0, stream, in_len, out_cap, nblocks,
-                           order);
+        hipLaunchKernelGGL(lz4mi::lz4mi_block_order_kernel, dim3(1), dim3(1024), 0, stream, b.in_len, b.out_cap,
+                           nblocks, order);
         a.order = order;
     }
     hipLaunchKernelGGL(lz4mi::lz4mi_decompress_kernel, dim3(nblocks), dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 
-extern "C" hipError_t lz4mi_launch_expand(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*, const uint64_t*,
-                                          const uint32_t*,
-                                          const uint8_t*, uint32_t, uint32_t*, int32_t*, const uint4*, const uint32_t*,
-                                          lz4mi::SegRec*, uint32_t, uint32_t, uint32_t*, uint32_t, uint32_t*, int,
-                                          uint32_t**, uint32_t, hipStream_t);
-
 // A small batch in LZ4 spec or reference mode (lz4mi_expand.hip): each block within the export
 // limits (x_in_max compressed, x_out_max output bytes, ratio < 32) is parsed by up to kSegMax
 // waves, one per ~kSegTarget bytes of its compressed block (seg_geom), which export its
 // sequences instead of writing them; the whole GPU then computes the output by pointer jumping.
-// Other blocks are decoded by the same launch as usual. `xs` scratch (lz4mi_small_scratch_bytes):
-// the blocks' sequence entries, their counts, first wrong segments and segment records,
-// nblocks * x_out_max pointers, and the output kernels' flags.
+// Other blocks are decoded by the same launch as usual. `xs`: scratch of
+// lz4mi_small_scratch_bytes, laid out by x_layout (lz4mi_launch.h).
 using lz4mi::kSegMax;
-static size_t small_meta_bytes(uint32_t nblocks) {   // counts, first wrong segments, segment records
-    return ((size_t)nblocks * 8 + (size_t)nblocks * kSegMax * sizeof(lz4mi::SegRec) + 255) / 256 * 256;
-}
 extern "C" size_t lz4mi_small_scratch_bytes(uint32_t nblocks, uint32_t x_in_max, uint32_t x_out_max) {
-    const size_t seqs = (size_t)nblocks * lz4mi::seg_block_capacity(x_in_max) * 16;
-    return (seqs + 255) / 256 * 256 + small_meta_bytes(nblocks) + (size_t)nblocks * x_out_max * 4 +
-           128 + ((size_t)nblocks + 63) / 64 * 512 + (size_t)nblocks * (x_out_max / 16) + 256;
+    return lz4mi::x_layout(nblocks, x_in_max, x_out_max, false).total;
 }
-extern "C" hipError_t lz4mi_launch_decompress_small(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                                    uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                                    const uint8_t* dict, uint32_t dict_len, uint32_t* out_len,
-                                                    int32_t* status, uint32_t nblocks, uint32_t x_in_max,
-                                                    uint32_t x_out_max, void* xs, int force_reparse, int f1,
-                                                    hipStream_t stream) {
-    using lz4mi::SegRec;
-    if (nblocks == 0) return hipSuccess;
-    const uint32_t stride = lz4mi::seg_block_capacity(x_in_max);
-    uint8_t* p = (uint8_t*)xs;
-    uint4* xseq = (uint4*)p;
-    p += ((size_t)nblocks * stride * 16 + 255) / 256 * 256;
-    uint32_t* xcnt = (uint32_t*)p;
-    uint32_t* xfirst = xcnt + nblocks;
-    SegRec* xrec = (SegRec*)(xfirst + nblocks);
-    hipError_t e = hipMemsetAsync(p, 0, small_meta_bytes(nblocks), stream);   // exported; records not final
-    if (e != hipSuccess) return e;
-    p += small_meta_bytes(nblocks);
-    uint32_t* ptr = (uint32_t*)p;
-    p += (size_t)nblocks * x_out_max * 4;
-    uint32_t* aux = (uint32_t*)p;   // jump rounds: round flags, check results, per-thread done bytes
-    // (f1check: a block past the export limits is decoded by its segment-0 wave in the caller's mode)
-    lz4mi::DecArgs a{in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks,
-                     nblocks > 1 ? 1 : 0, f1};
-    a.xseq = xseq;
-    a.xcnt = xcnt;
-    a.xrec = xrec;
-    a.xseq_stride = stride;
+extern "C" size_t lz4mi_linked_scratch_bytes(uint32_t nblocks, uint32_t x_in_max, uint32_t x_out_max) {
+    return lz4mi::x_layout(nblocks, x_in_max, x_out_max, true).total;
+}
+
+// The parse of an exported pass with `kernel` (lz4mi_decompress_x_kernel, or ..._xl_kernel for a
+// linked window); `a`: the blocks, the export fields are set here from the layout. The caller has
+// zeroed xcnt, xfirst and xrec (zero_parse_meta).
+// phase 0: every segment speculatively; the check; phase 1: the segments from the first
+// wrong entry on (an empty launch when there is none). A phase-1 wave waits only for its
+// predecessor, whose workgroup index is lower (dispatched first): the wait always ends.
+static hipError_t zero_parse_meta(const XLayout& L, void* xs, hipStream_t stream) {   // exported; records not final
+    return hipMemsetAsync(L.xcnt.in<uint8_t>(xs), 0, L.ptr.off - L.xcnt.off, stream);
+}
+static hipError_t parse_exported(DecArgs a, const XLayout& L, void* xs, int force_reparse, void (*kernel)(DecArgs),
+                                 hipStream_t stream) {
+    a.xseq = L.xseq.in<uint4>(xs);
+    a.xcnt = L.xcnt.in<uint32_t>(xs);
+    a.xrec = L.xrec.in<lz4mi::SegRec>(xs);
+    a.xseq_stride = L.stride;
     a.xsegs = kSegMax;
-    a.x_in_max = x_in_max;
-    a.x_out_max = x_out_max;
-    a.xfirst = xfirst;
-    a.xfirst_w = xfirst;
+    a.x_in_max = L.x_in_max;
+    a.x_out_max = L.x_out_max;
+    a.xfirst = L.xfirst.in<uint32_t>(xs);
+    a.xfirst_w = L.xfirst.in<uint32_t>(xs);
     a.xforce = force_reparse;
+    const dim3 grid(a.nblocks * kSegMax);
+    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(lz4mi::lz4mi_xverify_kernel, dim3(a.nblocks), dim3(64), 0, stream, a);
+    // phase 2: the segments whose guesses disagree, re-parsed at once, then the check again;
+    // phase 1 chains what is left (a second phase-2 pass: ~11 us of empty launches per call
+    // once the guesses restart past impossible tokens)
+    a.xphase = 2;
+    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(lz4mi::lz4mi_xverify_kernel, dim3(a.nblocks), dim3(64), 0, stream, a);
+    a.xphase = 1;
+    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lz4mi_launch_decompress_small(const Batch& b, uint32_t x_in_max, uint32_t x_out_max, void* xs,
+                                                    int force_reparse, int f1, hipStream_t stream) {
+    const uint32_t nblocks = b.nblocks;
+    if (nblocks == 0) return hipSuccess;
+    const XLayout L = lz4mi::x_layout(nblocks, x_in_max, x_out_max, false);
+    hipError_t e = zero_parse_meta(L, xs, stream);
+    if (e != hipSuccess) return e;
+    // (f1check: a block past the export limits is decoded by its segment-0 wave in the caller's mode)
+    DecArgs a = dec_args(b, nblocks > 1 ? 1 : 0, f1);
     // from 64 blocks on, nearly incompressible blocks (compressed >= 15/16 of the output: random data) go to one
     // wave each too: 4 MiB of literal pointers cost more than a wave's copy once there are many such blocks
     // (random 64 / 192 blocks 1.76 / 4.79 -> 0.92 / 1.19 ms, the 50/50 mix 192 blocks 6.16 -> 4.83; below 64 a
     // mix loses: the paced one-wave copies become the critical path -- 32 blocks 1.43 -> 1.62; round 6, profiles/r06fl)
     a.x_flat1 = nblocks >= 64 ? 1 : 0;
-    // phase 0: every segment speculatively; the check; phase 1: the segments from the first
-    // wrong entry on (an empty launch when there is none). A phase-1 wave waits only for its
-    // predecessor, whose workgroup index is lower (dispatched first): the wait always ends.
-    const dim3 grid(nblocks * kSegMax);
-    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_x_kernel, grid, dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(lz4mi::lz4mi_xverify_kernel, dim3(nblocks), dim3(64), 0, stream, a);
-    // phase 2: the segments whose guesses disagree, re-parsed at once, then the check again;
-    // phase 1 chains what is left (a second phase-2 pass: ~11 us of empty launches per call
-    // once the guesses restart past impossible tokens)
-    a.xphase = 2;
-    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_x_kernel, grid, dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(lz4mi::lz4mi_xverify_kernel, dim3(nblocks), dim3(64), 0, stream, a);
-    a.xphase = 1;
-    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_x_kernel, grid, dim3(64), 0, stream, a);
-    e = hipGetLastError();
+    e = parse_exported(a, L, xs, force_reparse, lz4mi::lz4mi_decompress_x_kernel, stream);
     if (e != hipSuccess) return e;
-    uint32_t* redo = nullptr;
-    e = lz4mi_launch_expand(in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, xseq, xcnt, xrec,
-                            kSegMax, stride, ptr, x_out_max, aux, f1, &redo, nblocks, stream);
+    e = lz4mi_launch_expand(b, L, xs, false, f1, 0, stream);
     if (e != hipSuccess || !f1) return e;
     // reference mode (LZ4MI_JS_EXACT): the double-copy-tail rewrites were applied to the pointers
     // (lz4mi_xf1ptr_kernel); a block with a rewrite reading before the block is decoded again by the
     // batch kernel (LZ4MI_ERR_CROSS_BLOCK when batched); the launch is empty when there is none
-    lz4mi::DecArgs r{in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks,
-                     nblocks > 1 ? 1 : 0, 1};
-    r.redo = redo;
+    DecArgs r = dec_args(b, nblocks > 1 ? 1 : 0, 1);
+    r.redo = L.redo.in<uint32_t>(xs);
     hipLaunchKernelGGL(lz4mi::lz4mi_decompress_kernel, dim3(nblocks), dim3(64), 0, stream, r);
     return hipGetLastError();
 }
@@ -2280,65 +2272,18 @@ extern "C" hipError_t lz4mi_launch_decompress_small(const uint8_t* in, const uin
 // lz4mi_linked_scratch_bytes; its first 256 bytes hold the call's state (zeroed by the caller
 // before the first window: a failure in one window fails the blocks of the later ones).
 // has_prev: the arrays hold an earlier block of the same call before this window's first.
-extern "C" hipError_t lz4mi_launch_linked_prep(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
-                                               const uint64_t*, const uint32_t*, uint32_t*, int32_t*, uint32_t, uint32_t,
-                                               uint32_t, int, int, uint32_t*, uint32_t*, hipStream_t);
-extern "C" hipError_t lz4mi_launch_expand_linked(const uint8_t*, const uint64_t*, const uint32_t*, uint8_t*,
-                                                 const uint64_t*, const uint32_t*, const uint8_t*, uint32_t, uint32_t*,
-                                                 int32_t*, const uint4*, const uint32_t*, lz4mi::SegRec*, uint32_t,
-                                                 uint32_t, uint32_t*, uint32_t, uint32_t*, uint32_t*, int, uint32_t,
-                                                 hipStream_t);
-static size_t linked_head_bytes(uint32_t nblocks) { return (256 + (size_t)nblocks * 8 + 255) / 256 * 256; }
-extern "C" size_t lz4mi_linked_scratch_bytes(uint32_t nblocks, uint32_t x_in_max, uint32_t x_out_max) {
-    return linked_head_bytes(nblocks) + lz4mi_small_scratch_bytes(nblocks, x_in_max, x_out_max);
-}
-extern "C" hipError_t lz4mi_launch_decompress_linked(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                                     uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                                     const uint8_t* dict, uint32_t dict_len, uint32_t* out_len,
-                                                     int32_t* status, uint32_t nblocks, uint32_t x_in_max,
-                                                     uint32_t x_out_max, void* xs, int force_reparse, int frame_words,
-                                                     int has_prev, hipStream_t stream) {
-    using lz4mi::SegRec;
-    if (nblocks == 0) return hipSuccess;
-    const uint32_t stride = lz4mi::seg_block_capacity(x_in_max);
-    uint32_t* xl = (uint32_t*)xs;
-    uint8_t* p = (uint8_t*)xs + linked_head_bytes(nblocks);
-    uint4* xseq = (uint4*)p;
-    p += ((size_t)nblocks * stride * 16 + 255) / 256 * 256;
-    uint32_t* xcnt = (uint32_t*)p;
-    uint32_t* xfirst = xcnt + nblocks;
-    SegRec* xrec = (SegRec*)(xfirst + nblocks);
-    hipError_t e = hipMemsetAsync(p, 0, small_meta_bytes(nblocks), stream);
-    if (e != hipSuccess) return e;
-    p += small_meta_bytes(nblocks);
-    uint32_t* ptr = (uint32_t*)p;
-    p += (size_t)nblocks * x_out_max * 4;
-    uint32_t* aux = (uint32_t*)p;
-    e = lz4mi_launch_linked_prep(in, in_off, in_len, out, out_off, out_cap, out_len, status, nblocks, x_in_max, x_out_max,
-                                 frame_words, has_prev, xl, xcnt, stream);
+extern "C" hipError_t lz4mi_launch_decompress_linked(const Batch& b, uint32_t x_in_max, uint32_t x_out_max, void* xs,
+                                                     int force_reparse, int frame_words, int has_prev,
+                                                     hipStream_t stream) {
+    if (b.nblocks == 0) return hipSuccess;
+    const XLayout L = lz4mi::x_layout(b.nblocks, x_in_max, x_out_max, true);
+    hipError_t e = zero_parse_meta(L, xs, stream);
+    if (e == hipSuccess) e = lz4mi_launch_linked_prep(b, L, xs, frame_words, has_prev, stream);
     if (e != hipSuccess) return e;
     // the parse reads the lengths the prep wrote (no stored bit; a block that is not parsed is skipped)
-    lz4mi::DecArgs a{in, in_off, xl + 8, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks, 0, 0};
-    a.xseq = xseq;
-    a.xcnt = xcnt;
-    a.xrec = xrec;
-    a.xseq_stride = stride;
-    a.xsegs = kSegMax;
-    a.x_in_max = x_in_max;
-    a.x_out_max = x_out_max;
-    a.xfirst = xfirst;
-    a.xfirst_w = xfirst;
-    a.xforce = force_reparse;
-    const dim3 grid(nblocks * kSegMax);
-    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_xl_kernel, grid, dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(lz4mi::lz4mi_xverify_kernel, dim3(nblocks), dim3(64), 0, stream, a);
-    a.xphase = 2;
-    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_xl_kernel, grid, dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(lz4mi::lz4mi_xverify_kernel, dim3(nblocks), dim3(64), 0, stream, a);
-    a.xphase = 1;
-    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_xl_kernel, grid, dim3(64), 0, stream, a);
-    e = hipGetLastError();
+    DecArgs a = dec_args(b, 0, 0);
+    a.in_len = L.head.in<uint32_t>(xs) + 8;
+    e = parse_exported(a, L, xs, force_reparse, lz4mi::lz4mi_decompress_xl_kernel, stream);
     if (e != hipSuccess) return e;
-    return lz4mi_launch_expand_linked(in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, xseq,
-                                      xcnt, xrec, kSegMax, stride, ptr, x_out_max, aux, xl, frame_words, nblocks, stream);
+    return lz4mi_launch_expand(b, L, xs, true, 0, frame_words, stream);
 }

@@ -8,6 +8,7 @@
 // frame loop (src/buffer/bufferDecompress.js:133-192) runs them.
 #include "lz4mi_common.h"
 #include "lz4mi_decompress.h"
+#include "lz4mi_launch.h"
 
 namespace lz4mi {
 

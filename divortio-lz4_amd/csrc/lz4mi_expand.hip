@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "lz4mi_decompress.h"
+#include "lz4mi_launch.h"
 
 namespace lz4mi {
 
@@ -684,106 +685,83 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_chase_linked_kernel(ExpArgs a
   }
 }
 
+static_assert(kXBytes == 16, "x_layout (lz4mi_launch.h) sizes `done` at one byte per 16 output bytes");
+
+// The kernels' arguments for the blocks of `b`; the output launcher fills in the rest
+static ExpArgs exp_args(const Batch& b) {
+    return ExpArgs{b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.dict, b.dict_len, b.out_len, b.status};
+}
+
 }  // namespace lz4mi
 
-// The output phase of an exported small batch: the checks with absolute positions, status,
-// expand, up to kJumpRounds jump rounds (each returns at once when the previous one left
-// nothing to follow; a thread whose 16 bytes are resolved at once too), gather. `aux`: the round
-// flags (32 words), nblocks check results, then nblocks * x_out_max / 16 done bytes.
-extern "C" hipError_t lz4mi_launch_expand(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint8_t* out,
-                                          const uint64_t* out_off, const uint32_t* out_cap, const uint8_t* dict,
-                                          uint32_t dict_len, uint32_t* out_len, int32_t* status, const uint4* xseq,
-                                          const uint32_t* xcnt, lz4mi::SegRec* xrec, uint32_t nseg,
-                                          uint32_t xseq_stride, uint32_t* ptr, uint32_t x_out_max, uint32_t* aux,
-                                          int f1, uint32_t** redo_out, uint32_t nblocks, hipStream_t stream) {
+// The output phase of an exported small batch or (linked) of a linked window, after the parse:
+// the checks with absolute positions (linked: no cross-block check), statuses, linked: the first
+// failing block and the stored blocks, then expand, up to kJumpRounds jump rounds (each returns at
+// once when the previous one left nothing to follow; a thread whose 16 bytes are resolved at once
+// too), chase and gather (linked: over the window's pointer array). `xs`: the pass's scratch (L).
+// f1: reference mode (small path only); frame_words: linked only.
+extern "C" hipError_t lz4mi_launch_expand(const lz4mi::Batch& b, const lz4mi::XLayout& L, void* xs, bool linked,
+                                          int f1, int frame_words, hipStream_t stream) {
     using namespace lz4mi;
+    const uint32_t nblocks = b.nblocks, x_out_max = L.x_out_max, nseg = kSegMax;
     if (nblocks == 0) return hipSuccess;
-    uint32_t* flags = aux;
-    uint32_t* best = flags + 32;
-    uint32_t* redo = best + ((nblocks + 63) & ~63u);
-    uint8_t* done = (uint8_t*)(redo + ((nblocks + 63) & ~63u));
-    *redo_out = redo;
-    ExpArgs a{in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, xseq, xcnt, xrec, nseg, xseq_stride,
-              ptr, x_out_max, done, flags, best, nblocks * (x_out_max / kTile),
-              (uint32_t)__builtin_ctz(x_out_max / kTile)};
-    if ((x_out_max & (x_out_max - 1)) || x_out_max < kTile) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t) * 32, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(done, 0, (size_t)nblocks * (x_out_max / kXBytes), stream);
+    if ((x_out_max & (x_out_max - 1)) || x_out_max < kTile ||
+        (linked && (uint64_t)nblocks * x_out_max > (1ull << 31)))
+        return hipErrorInvalidValue;
+    uint32_t* xl = L.head.in<uint32_t>(xs);
+    uint32_t* redo = L.redo.in<uint32_t>(xs);
+    ExpArgs a = exp_args(b);
+    a.xseq = L.xseq.in<uint4>(xs);
+    a.xcnt = L.xcnt.in<uint32_t>(xs);
+    a.xrec = L.xrec.in<SegRec>(xs);
+    a.nseg = nseg;
+    a.xseq_stride = L.stride;
+    a.ptr = L.ptr.in<uint32_t>(xs);
+    a.x_out_max = x_out_max;
+    a.done = L.done.in<uint8_t>(xs);
+    a.flags = L.flags.in<uint32_t>(xs);
+    a.best = L.best.in<uint32_t>(xs);
+    a.ntiles = nblocks * (x_out_max / kTile);
+    a.tshift = (uint32_t)__builtin_ctz(x_out_max / kTile);
+    if (linked) {   // the lengths the prep wrote, and the window's bases
+        a.in_len = xl + 8;
+        a.lbase = xl + 8 + nblocks;
+        a.win = (const uint64_t*)(xl + 2);
+    }
+    const int isolate = !linked && nblocks > 1 ? 1 : 0;
+    hipError_t e = hipMemsetAsync(a.flags, 0, L.flags.bytes, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.done, 0, L.done.bytes, stream);
     if (e == hipSuccess && f1) e = hipMemsetAsync(redo, 0, sizeof(uint32_t) * nblocks, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(lz4mi_xbase_kernel, dim3(nblocks), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(lz4mi_xcheck_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a, nblocks > 1 ? 1 : 0);
+    hipLaunchKernelGGL(lz4mi_xcheck_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a, isolate);
     hipLaunchKernelGGL(lz4mi_xstatus_kernel, dim3(nblocks), dim3(64), 0, stream, a);
+    if (linked) hipLaunchKernelGGL(lz4mi_linked_fail_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, xl);
+    if (linked && frame_words)
+        hipLaunchKernelGGL(lz4mi_linked_stored_kernel, dim3(64, nblocks), dim3(256), 0, stream, a, b.in_len);
     const dim3 grid(min(a.ntiles, kXGrid));
-    hipLaunchKernelGGL(lz4mi_expand_kernel, grid, dim3(kXThreads), 0, stream, a);
+    hipLaunchKernelGGL(linked ? lz4mi_expand_linked_kernel : lz4mi_expand_kernel, grid, dim3(kXThreads), 0, stream, a);
     if (f1)
-        hipLaunchKernelGGL(lz4mi_xf1ptr_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a, nblocks > 1 ? 1 : 0,
-                           redo);
-    for (int r = 0; r < kJumpRounds; ++r) hipLaunchKernelGGL(lz4mi_jump_kernel, grid, dim3(kXThreads), 0, stream, a, r);
-    hipLaunchKernelGGL(lz4mi_chase_kernel, grid, dim3(kXThreads), 0, stream, a);
-    hipLaunchKernelGGL(lz4mi_gather_kernel, grid, dim3(kXThreads), 0, stream, a);
-    return hipGetLastError();
-}
-
-// Linked mode, before the parse: the window's bases and which blocks are parsed (xl: see
-// lz4mi_linked_prep_kernel; 8 + 2 * nblocks words).
-extern "C" hipError_t lz4mi_launch_linked_prep(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
-                                               uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                               uint32_t* out_len, int32_t* status, uint32_t nblocks, uint32_t x_in_max,
-                                               uint32_t x_out_max, int fw, int has_prev, uint32_t* xl, uint32_t* xcnt,
-                                               hipStream_t stream) {
-    using namespace lz4mi;
-    ExpArgs a{};
-    a.in = in;
-    a.in_off = in_off;
-    a.in_len = in_len;
-    a.out = out;
-    a.out_off = out_off;
-    a.out_cap = out_cap;
-    a.out_len = out_len;
-    a.status = status;
-    a.x_out_max = x_out_max;
-    hipLaunchKernelGGL(lz4mi_linked_prep_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, x_in_max, fw, has_prev, xl,
-                       xcnt);
-    return hipGetLastError();
-}
-
-// The output phase of a linked window (after the parse of the blocks lz4mi_linked_prep_kernel left
-// exported): checks (absolute positions; no cross-block check), statuses, the first failing block,
-// the stored blocks, then expand, jump rounds, chase and gather over the window's pointer array.
-extern "C" hipError_t lz4mi_launch_expand_linked(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_words,
-                                                 uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
-                                                 const uint8_t* dict, uint32_t dict_len, uint32_t* out_len,
-                                                 int32_t* status, const uint4* xseq, const uint32_t* xcnt,
-                                                 lz4mi::SegRec* xrec, uint32_t nseg, uint32_t xseq_stride, uint32_t* ptr,
-                                                 uint32_t x_out_max, uint32_t* aux, uint32_t* xl, int fw,
-                                                 uint32_t nblocks, hipStream_t stream) {
-    using namespace lz4mi;
-    if (nblocks == 0) return hipSuccess;
-    if ((x_out_max & (x_out_max - 1)) || x_out_max < kTile || (uint64_t)nblocks * x_out_max > (1ull << 31))
-        return hipErrorInvalidValue;
-    uint32_t* flags = aux;
-    uint32_t* best = flags + 32;
-    uint32_t* redo = best + ((nblocks + 63) & ~63u);
-    uint8_t* done = (uint8_t*)(redo + ((nblocks + 63) & ~63u));
-    ExpArgs a{in, in_off, xl + 8, out, out_off, out_cap, dict, dict_len, out_len, status, xseq, xcnt, xrec, nseg,
-              xseq_stride, ptr, x_out_max, done, flags, best, nblocks * (x_out_max / kTile),
-              (uint32_t)__builtin_ctz(x_out_max / kTile), xl + 8 + nblocks, (const uint64_t*)(xl + 2)};
-    hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t) * 32, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(done, 0, (size_t)nblocks * (x_out_max / kXBytes), stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lz4mi_xbase_kernel, dim3(nblocks), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(lz4mi_xcheck_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a, 0);
-    hipLaunchKernelGGL(lz4mi_xstatus_kernel, dim3(nblocks), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(lz4mi_linked_fail_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, xl);
-    if (fw) hipLaunchKernelGGL(lz4mi_linked_stored_kernel, dim3(64, nblocks), dim3(256), 0, stream, a, in_words);
-    const dim3 grid(min(a.ntiles, kXGrid));
-    hipLaunchKernelGGL(lz4mi_expand_linked_kernel, grid, dim3(kXThreads), 0, stream, a);
+        hipLaunchKernelGGL(lz4mi_xf1ptr_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a, isolate, redo);
     for (int r = 0; r < kJumpRounds; ++r)
-        hipLaunchKernelGGL(lz4mi_jump_linked_kernel, grid, dim3(kXThreads), 0, stream, a, r);
-    hipLaunchKernelGGL(lz4mi_chase_linked_kernel, grid, dim3(kXThreads), 0, stream, a);
-    hipLaunchKernelGGL(lz4mi_linked_fail_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, xl);
-    hipLaunchKernelGGL(lz4mi_gather_linked_kernel, grid, dim3(kXThreads), 0, stream, a);
+        hipLaunchKernelGGL(linked ? lz4mi_jump_linked_kernel : lz4mi_jump_kernel, grid, dim3(kXThreads), 0, stream, a, r);
+    hipLaunchKernelGGL(linked ? lz4mi_chase_linked_kernel : lz4mi_chase_kernel, grid, dim3(kXThreads), 0, stream, a);
+    if (linked) hipLaunchKernelGGL(lz4mi_linked_fail_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, xl);
+    hipLaunchKernelGGL(linked ? lz4mi_gather_linked_kernel : lz4mi_gather_kernel, grid, dim3(kXThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+// Linked mode, before the parse: the window's bases and which blocks are parsed (the head of the
+// scratch, xl: see lz4mi_linked_prep_kernel; 8 + 2 * nblocks words).
+extern "C" hipError_t lz4mi_launch_linked_prep(const lz4mi::Batch& b, const lz4mi::XLayout& L, void* xs, int fw,
+                                               int has_prev, hipStream_t stream) {
+    using namespace lz4mi;
+    ExpArgs a = exp_args(b);
+    a.dict = nullptr;   // (the prep reads no dictionary)
+    a.dict_len = 0;
+    a.x_out_max = L.x_out_max;
+    hipLaunchKernelGGL(lz4mi_linked_prep_kernel, dim3(1), dim3(256), 0, stream, a, b.nblocks, L.x_in_max, fw, has_prev,
+                       L.head.in<uint32_t>(xs), L.xcnt.in<uint32_t>(xs));
     return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 // length (pay_off/pay_len) and its checksum position (sum_off) for the batched
 // XXH32 kernel that fills them in.
 #include "lz4mi_common.h"
+#include "lz4mi_launch.h"
 
 namespace lz4mi {
 

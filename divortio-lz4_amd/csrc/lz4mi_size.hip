@@ -26,6 +26,7 @@
 // increase, the certification settles one more lane per pass.
 #include "../../include/lz4mi.h"
 #include "lz4mi_common.h"
+#include "lz4mi_launch.h"
 
 namespace lz4mi {
 namespace size_pass {

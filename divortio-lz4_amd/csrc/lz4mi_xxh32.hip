@@ -12,6 +12,7 @@
 // rotl(rotl(rotl(rotl(v1,1)+v2,7)+v3,12)+v4,18)); `standard` selects the
 // XXH32 specification's rotl(v1,1)+rotl(v2,7)+rotl(v3,12)+rotl(v4,18).
 #include "lz4mi_common.h"
+#include "lz4mi_launch.h"
 
 namespace lz4mi {
 

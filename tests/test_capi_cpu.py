@@ -151,3 +151,69 @@ def test_streaming_xxh32_length_modes():
         b = lz4mi.XXHash32(3, standard=std, len64=True).update(data).digest()
         assert a == b == lz4mi.xxh32(data, 3, standard=std)
     assert lz4mi.XXHash32(0, standard=True).update(data).digest() == O.xxh32_std(data)
+
+
+# lz4mi_small_scratch_bytes / lz4mi_linked_scratch_bytes of the commit before the scratch layout
+# became one struct (csrc/lz4mi_launch.h x_layout), read from a build of that commit:
+# (nblocks, x_in_max, x_out_max) -> (small, linked)
+SCRATCH_TOTALS = {
+    (1, 65536, 65536): (8002176, 8002688),
+    (63, 65536, 65536): (504054912, 504055680),
+    (64, 65536, 65536): (512055680, 512056448),
+    (65, 65536, 65536): (520057472, 520058496),
+    (192, 65536, 65536): (1536166272, 1536168064),
+    (1, 131072, 1 << 20): (12345216, 12345728),
+    (63, 131072, 1 << 20): (777671552, 777672320),
+    (64, 131072, 1 << 20): (790015360, 790016128),
+    (65, 131072, 1 << 20): (802360192, 802361216),
+    (192, 131072, 1 << 20): (2370045312, 2370047104),
+    (1, 4210768, 4 << 20): (46883200, 46883712),
+    (63, 4210768, 4 << 20): (2953559424, 2953560192),
+    (64, 4210768, 4 << 20): (3000441216, 3000441984),
+    (65, 4210768, 4 << 20): (3047324032, 3047325056),
+    (192, 4210768, 4 << 20): (9001322880, 9001324672),
+}
+K_SEG_MAX, SEG_REC_BYTES = 256, 48            # csrc/lz4mi_decompress.h: kSegMax, sizeof(SegRec)
+
+
+def _seg_block_capacity(x_in_max):           # csrc/lz4mi_decompress.h
+    return x_in_max // 3 + K_SEG_MAX * 1800
+
+
+@pytest.mark.parametrize("key", sorted(SCRATCH_TOTALS))
+def test_small_path_scratch_layout(key):
+    """The scratch of a small-path pass and of a linked window: the totals are the ones recorded
+    above, and the regions of the layout behind them (lz4mi_debug_layout) ascend without overlap,
+    end within the total, keep their alignment and hold what their kernels index."""
+    n, xi, xo = key
+    L = lz4mi.lib()
+    for f in (L.lz4mi_small_scratch_bytes, L.lz4mi_linked_scratch_bytes):
+        f.restype, f.argtypes = ctypes.c_size_t, [ctypes.c_uint32] * 3
+    L.lz4mi_debug_layout.argtypes = [ctypes.c_uint32] * 3 + [ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]
+    assert (L.lz4mi_small_scratch_bytes(n, xi, xo), L.lz4mi_linked_scratch_bytes(n, xi, xo)) == SCRATCH_TOTALS[key]
+    pad64 = (n + 63) & ~63
+    names = ("head", "xseq", "xcnt", "xfirst", "xrec", "ptr", "flags", "best", "redo", "done")
+    for linked in (0, 1):
+        v = (ctypes.c_ulonglong * 21)()
+        assert L.lz4mi_debug_layout(n, xi, xo, linked, v) == 0
+        reg = {name: (int(v[2 * k]), int(v[2 * k + 1])) for k, name in enumerate(names)}
+        total = int(v[20])
+        assert total == SCRATCH_TOTALS[key][linked]
+        at = 0
+        for name in names:                                   # ascending, disjoint, within the total
+            off, size = reg[name]
+            assert off >= at, (name, linked)
+            at = off + size
+        assert at <= total
+        assert reg["head"][1] >= ((8 + 2 * n) * 4 if linked else 0)   # the call's state and the window's 2n words
+        assert reg["xseq"][0] % 256 == 0 and reg["ptr"][0] % 256 == 0 and reg["done"][0] % 4 == 0
+        assert reg["xseq"][1] >= n * _seg_block_capacity(xi) * 16
+        # xcnt, xfirst and xrec are one run of memory (zeroed together, up to ptr)
+        assert reg["xfirst"][0] == reg["xcnt"][0] + 4 * n and reg["xrec"][0] == reg["xfirst"][0] + 4 * n
+        assert reg["xcnt"][1] >= 4 * n and reg["xfirst"][1] >= 4 * n
+        assert reg["xrec"][1] >= n * K_SEG_MAX * SEG_REC_BYTES
+        assert reg["ptr"][0] - reg["xcnt"][0] >= n * 8 + n * K_SEG_MAX * SEG_REC_BYTES
+        assert reg["ptr"][1] >= n * xo * 4
+        assert reg["flags"][1] >= 32 * 4
+        assert reg["best"][1] >= pad64 * 4 and reg["redo"][1] >= pad64 * 4
+        assert reg["done"][1] >= n * xo // 16

@@ -5,6 +5,7 @@ reference's decompressBlock, blockDecompress.js:55-272): bytes, lengths and stat
 generator (incl. long offset-1 runs, far copies), history before the output offset and
 dictionaries, corrupted streams, and a batch mixing exported blocks with one past the export
 limit (decoded by the same launch as usual)."""
+import ctypes
 import os
 
 import numpy as np
@@ -227,6 +228,95 @@ def test_small_batch_reference_mode_matches_reference_decoder():
             assert st[j] == est and lens[j] == ew, (sel, i, st[j], est)
             if est == 0:
                 assert np.array_equal(outs[j], eo[:ew]), (sel, i)
+
+
+SEAM_KINDS = ("tiles216", "text", "random", "runs", "repetitive", "copy")
+
+
+@pytest.fixture(scope="module")
+def seam_blocks():
+    """66 independent blocks of 5-64 KiB raw over the generators, the last one (copy) of 70 KiB, with
+    the oracle's spec and reference-mode decodes; and 65 dependent blocks of 5-70 KiB (one table
+    carried along a buffer that mixes the generators) with the oracle's decode in index order."""
+    rng = np.random.default_rng(6564)
+    sizes = [int(rng.integers(5 << 10, (64 << 10) + 1)) for _ in range(65)] + [70 << 10]
+    srcs = [O.generate(SEAM_KINDS[k % 6], 100 + k, n) for k, n in enumerate(sizes)]
+    comps = [O.compress_block_bytes(s) for s in srcs]
+    spec = [O.decompress_block(c, s.size) for c, s in zip(comps, srcs)]
+    ref = [O.decompress_block(c, s.size, js_compat=True) for c, s in zip(comps, srcs)]
+    assert all(c.size * 16 >= s.size * 15 for c, s in zip(comps[2::6], srcs[2::6]))   # random: nearly incompressible
+    # the copy blocks have double-copy-tail rewrites (SURVEY F1) that change their output
+    assert all(not np.array_equal(r[2][:r[1]], s) for r, s in zip(ref[5::6], srcs[5::6]))
+    dsizes = [int(rng.integers(5 << 10, (70 << 10) + 1)) for _ in range(65)]
+    data = np.concatenate([O.generate(SEAM_KINDS[k % 6], 200 + k, n) for k, n in enumerate(dsizes)])
+    table = np.zeros(16384, dtype=np.int32)
+    pay, pos = [], 0
+    out = np.zeros(data.size, dtype=np.uint8)
+    for n in dsizes:
+        w, o, table = O.compress_block(data, pos, n, table)
+        pay.append(o[:w].copy())
+        est, ew, _ = O.decompress_block(pay[-1], n, out=out[:pos + n], out_off=pos)
+        assert est == 0 and ew == n
+        pos += n
+    assert np.array_equal(out, data)
+    return srcs, comps, spec, ref, pay, dsizes, data
+
+
+def _dev_decode(comps, caps, **kw):
+    """One device-pointer call on torch tensors, the slots back to back -> (statuses, outputs, lengths)."""
+    import torch
+    src, in_off, in_len = lz4mi._pack([lz4mi._u8(c) for c in comps])
+    caps = np.asarray(caps, dtype=np.int64)
+    out_off = np.concatenate([[0], np.cumsum(caps[:-1])]).astype(np.int64)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).cuda()
+    d_in, d_ioff, d_ilen = t(src, np.uint8), t(in_off, np.int64), t(in_len.view(np.int32), np.int32)
+    d_ooff, d_cap = t(out_off, np.int64), t(caps, np.int32)
+    d_out = torch.zeros(int(caps.sum()), dtype=torch.uint8, device="cuda")
+    d_len = torch.full((len(comps),), 77, dtype=torch.int32, device="cuda")
+    d_st = torch.full((len(comps),), 77, dtype=torch.int32, device="cuda")
+    lz4mi.decompress_blocks_dev(d_in.data_ptr(), d_ioff.data_ptr(), d_ilen.data_ptr(), d_out.data_ptr(),
+                                d_ooff.data_ptr(), d_cap.data_ptr(), d_len.data_ptr(), d_st.data_ptr(), len(comps),
+                                torch.cuda.current_stream().cuda_stream, **kw)
+    torch.cuda.synchronize()
+    out = d_out.cpu().numpy()
+    return d_st.cpu().numpy(), [out[o:o + c] for o, c in zip(out_off, caps)], d_len.cpu().numpy()
+
+
+@pytest.mark.parametrize("nblocks", [1, 63, 64, 65])
+def test_small_batch_layout_seams(seam_blocks, nblocks, monkeypatch):
+    """Batches at the seams of the scratch layout (csrc/lz4mi_launch.h x_layout): 1, 63, 64 and 65
+    blocks -- the check results and reference-mode marks are padded to 64 blocks, and from 64
+    blocks on the nearly incompressible blocks take one wave --, the first blocks of the list
+    (output limit 64 KiB with host pointers) and the last ones (the 70 KiB block: 128 KiB), in spec
+    and reference mode through host and device pointers (which size the scratch for 4 MiB blocks):
+    statuses, lengths and bytes equal the oracle's. Then as many dependent blocks, linked, in
+    windows of at most 64 blocks: 65 blocks are two windows, the second of one block with a
+    predecessor."""
+    pytest.importorskip("torch")
+    srcs, comps, spec, ref, pay, dsizes, data = seam_blocks
+    for first in (0, len(srcs) - nblocks):
+        sel = range(first, first + nblocks)
+        cs, caps = [comps[i] for i in sel], [srcs[i].size for i in sel]
+        for js_exact, want in ((False, spec), (True, ref)):
+            for call in (lz4mi.decompress_blocks, _dev_decode):
+                st, outs, lens = call(cs, caps, js_exact=js_exact)
+                for j, i in enumerate(sel):
+                    est, ew, eo = want[i]
+                    if js_exact and st[j] == lz4mi.ERR_CROSS_BLOCK:   # batched: a rewrite reaches before the block
+                        assert nblocks > 1 and SEAM_KINDS[i % 6] in ("text", "runs", "copy"), (first, i)
+                        continue
+                    assert st[j] == est == 0 and lens[j] == ew, (first, js_exact, call.__name__, i, st[j], lens[j])
+                    assert np.array_equal(outs[j][:ew], eo[:ew]), (first, js_exact, call.__name__, i)
+    monkeypatch.setenv("LZ4MI_LINKED_WINDOW", "64")
+    total = sum(dsizes[:nblocks])
+    for call in (lz4mi.decompress_blocks, _dev_decode):
+        st, outs, lens = call(pay[:nblocks], dsizes[:nblocks], linked=True)
+        assert not np.asarray(st).any() and [int(x) for x in lens] == dsizes[:nblocks], (call.__name__, st)
+        assert np.array_equal(np.concatenate(outs), data[:total]), call.__name__
+    if nblocks == 65:
+        stats = (ctypes.c_ulonglong * 4)()
+        lz4mi.lib().lz4mi_debug_linked_stats(stats)
+        assert stats[0] == 2                             # windows of the last call
 
 
 def test_small_batch_scratch_allocation_failure():
