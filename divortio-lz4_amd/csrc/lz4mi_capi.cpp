@@ -230,9 +230,13 @@ hipError_t decode_launch(const Batch& b, int mode, hipStream_t s, Scratch* order
 // failure has been written before it is marked, and the export limits are not checked.
 // in_max / out_max: the largest compressed block and capacity if the caller knows them (0: the
 // export limits); h_*: the host's copies of the arrays (nullptr with device pointers).
+// f1: LZ4MI_LINKED_EXACT, the reference decoder's bytes (lz4mi_expand.hip "linked reference mode"); the last
+// resort then decodes each block in reference mode, a lone-block LZ4MI_JS_EXACT decode, which rewrites the
+// bytes below the block as the contract's successive calls do.
 uint64_t g_linked_stats[4];   // the last linked call: windows, scratch bytes, x_in_max, x_out_max (lz4mi_debug_linked_stats)
+uint64_t g_linked_resumes;    // the last lz4mi_frame_decompress: linked calls issued again behind a refused block
 
-hipError_t linked_launch(const Batch& b, int fw, hipStream_t s, Scratch* small, uint32_t in_max, uint32_t out_max,
+hipError_t linked_launch(const Batch& b, int fw, int f1, hipStream_t s, Scratch* small, uint32_t in_max, uint32_t out_max,
                          const uint64_t* h_in_off = nullptr, const uint32_t* h_in_len = nullptr,
                          const uint64_t* h_out_off = nullptr, const uint32_t* h_out_cap = nullptr) {
     const XLimits x = export_limits(in_max, out_max);
@@ -265,7 +269,7 @@ hipError_t linked_launch(const Batch& b, int fw, hipStream_t s, Scratch* small, 
     g_linked_stats[3] = xo;
     if (!wmax) {
         for (uint32_t k = 0; k < nblocks; ++k) {
-            e = lz4mi_launch_decompress(b.slice(k, 1), fw ? 4 : 0, nullptr, s);
+            e = lz4mi_launch_decompress(b.slice(k, 1), (fw ? 4 : 0) | (f1 ? 2 : 0), nullptr, s);
             if (e != hipSuccess) return e;
         }
         return lz4mi_launch_linked_fail(b.out_len, b.status, nblocks, small->as<uint32_t>(), s);
@@ -284,7 +288,8 @@ hipError_t linked_launch(const Batch& b, int fw, hipStream_t s, Scratch* small, 
             }
             nb = k;
         }
-        e = lz4mi_launch_decompress_linked(b.slice(w0, nb), xi, xo, small->p, small_reparse_hook(), fw, w0 ? 1 : 0, s);
+        e = lz4mi_launch_decompress_linked(b.slice(w0, nb), xi, xo, small->p, small_reparse_hook(), fw, w0 ? 1 : 0, f1,
+                                           s);
         if (e != hipSuccess) return e;
         ++g_linked_stats[0];
         w0 += nb;
@@ -521,8 +526,9 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
         if (js || !(flags & LZ4MI_DEVICE_PTRS)) return LZ4MI_ERR_ARG;
         mode |= 4;
     }
-    const bool linked = (flags & LZ4MI_LINKED) != 0;
-    if (linked && (flags & (LZ4MI_JS_COMPAT | LZ4MI_JS_EXACT))) return LZ4MI_ERR_ARG;   // (spec mode only: see the header)
+    const bool lx = (flags & LZ4MI_LINKED_EXACT) != 0;   // (the reference's bytes for a linked batch: a flag of its own)
+    const bool linked = lx || (flags & LZ4MI_LINKED) != 0;
+    if (linked && (flags & (LZ4MI_JS_COMPAT | LZ4MI_JS_EXACT))) return LZ4MI_ERR_ARG;   // (see the header)
     if (nblocks == 0) return LZ4MI_OK;
     if (flags & LZ4MI_DEVICE_PTRS) {
         // the order scratch belongs to the stream: kernels of one stream use it in order
@@ -530,7 +536,7 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
         StreamCtx* c = stream_ctx(s);
         std::lock_guard<std::mutex> sl(c->mu);
         const Batch batch{in, in_off, in_len, out, out_off, out_cap, dict, dict_len, out_len, status, nblocks};
-        if (linked) LZ4MI_TRY(linked_launch(batch, (mode & 4) ? 1 : 0, s, &c->small, 0, 0));
+        if (linked) LZ4MI_TRY(linked_launch(batch, (mode & 4) ? 1 : 0, lx ? 1 : 0, s, &c->small, 0, 0));
         else LZ4MI_TRY(decode_launch(batch, mode, s, &c->order, &c->small));
         return LZ4MI_OK;
     }
@@ -552,7 +558,8 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
         lo = std::min<uint64_t>(lo, out_off[b]);
         hi = std::max<uint64_t>(hi, out_off[b] + out_cap[b]);
     }
-    uint64_t hist = std::min<uint64_t>(lo, 65536);
+    // (LZ4MI_LINKED_EXACT: a rewrite up to 4 bytes below the first block reads up to 65535 bytes below itself)
+    uint64_t hist = std::min<uint64_t>(lo, lx ? 65536 + 8 : 65536);
     uint64_t base = lo - hist, img = hi - base;
     lz4mi_advise_output(out + lo, hi - lo);
     std::vector<uint64_t> d_out_off(nblocks);
@@ -579,8 +586,8 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
     const Batch batch{st.in, st.in_off, st.in_len, g_ctx.out.as<uint8_t>(), st.more64, m_out_cap,
                   dlen ? g_ctx.aux.as<uint8_t>() : nullptr, dlen, m_out_len, m_status, nblocks};
     if (linked)
-        LZ4MI_TRY(linked_launch(batch, 0, s, &g_ctx.small, std::max(in_max, 1u), std::max(out_max, 1u), st.h_in_off.data(),
-                                in_len, d_out_off.data(), out_cap));
+        LZ4MI_TRY(linked_launch(batch, 0, lx ? 1 : 0, s, &g_ctx.small, std::max(in_max, 1u), std::max(out_max, 1u),
+                                st.h_in_off.data(), in_len, d_out_off.data(), out_cap));
     else
         LZ4MI_TRY(decode_launch(batch, mode, s, &g_ctx.order, &g_ctx.small, std::max(in_max, 1u), std::max(out_max, 1u)));
     LZ4MI_TRY(hipMemcpyAsync(out_len, m_out_len, 4ull * nblocks, hipMemcpyDeviceToHost, s));
@@ -596,7 +603,8 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
             uint64_t n = std::min<uint64_t>(out_len[b], out_cap[b]);
             // a lone block re-decoded reference-exactly may rewrite up to 7 bytes
             // before its start (F1 at the block's first match): copy those back too
-            const uint64_t pre = (mode == 2 && nblocks == 1) ? std::min<uint64_t>(d_out_off[b], 8) : 0;
+            // (LZ4MI_LINKED_EXACT: every block may, into its predecessor's slot, a gap or the caller's bytes)
+            const uint64_t pre = ((mode == 2 && nblocks == 1) || lx) ? std::min<uint64_t>(d_out_off[b], 8) : 0;
             if (n + pre) LZ4MI_TRY(hipMemcpyAsync(out + out_off[b] - pre, g_ctx.out.as<uint8_t>() + d_out_off[b] - pre,
                                                   n + pre, hipMemcpyDeviceToHost, s));
         }
@@ -610,6 +618,10 @@ int lz4mi_debug_linked_stats(unsigned long long* out) {
     for (int k = 0; k < 4; ++k) out[k] = g_linked_stats[k];
     return 0;
 }
+
+// The last lz4mi_frame_decompress with LZ4MI_LINKED_EXACT: how often the linked call was issued again for the
+// blocks behind a refused one (tests/test_gpu_linked_exact.py: at most once per stored block).
+unsigned long long lz4mi_debug_linked_resumes(void) { return g_linked_resumes; }
 
 // The scratch layout of a small-path pass or linked window (tests/test_capi_cpu.py): offset and bytes of the
 // head, xseq, xcnt, xfirst, xrec, ptr, flags, best, redo and done, then the total: 21 values.
@@ -837,11 +849,13 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     DeviceGuard dg;
     if (dg.status()) return dg.status();
     if (!(flags & LZ4MI_DEVICE_PTRS) || !info || (flags & LZ4MI_JS_COMPAT)) return LZ4MI_ERR_ARG;
-    const bool linked = (flags & LZ4MI_LINKED) != 0;
+    const bool lx = (flags & LZ4MI_LINKED_EXACT) != 0;
+    const bool linked = lx || (flags & LZ4MI_LINKED) != 0;
     if (linked && (flags & LZ4MI_JS_EXACT)) return LZ4MI_ERR_ARG;
     for (int k = 0; k < 8; ++k) info[k] = 0;
     hipStream_t s = pick_stream(stream);
-    const int mode = (flags & LZ4MI_JS_EXACT) ? 2 : 0;
+    const int mode = ((flags & LZ4MI_JS_EXACT) || lx) ? 2 : 0;   // (of the blocks decoded alone)
+    if (lx) g_linked_resumes = 0;
     // the header (<= 19 bytes) first: the content size bounds the number of blocks of the reference's layout
     uint8_t h[19] = {0};
     LZ4MI_TRY(hipMemcpyAsync(h, frame, std::min<uint64_t>(len, 19), hipMemcpyDeviceToHost, s));
@@ -902,7 +916,7 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     // frame order, the stored blocks lie in the gaps; sized for the frame's block_max, which a compressed
     // block of the reference's layout does not exceed: one that does is refused and decoded alone below)
     const Batch cb{frame, c_in_off, c_in_len, out, c_out_off, c_out_cap, nullptr, 0, d_out_len, d_status, nc};
-    if (nc && linked) LZ4MI_TRY(linked_launch(cb, 0, s, &c->small, (uint32_t)bmax, (uint32_t)bmax));
+    if (nc && linked) LZ4MI_TRY(linked_launch(cb, 0, lx ? 1 : 0, s, &c->small, (uint32_t)bmax, (uint32_t)bmax));
     else if (nc) LZ4MI_TRY(decode_launch(cb, mode, s, &c->order));
     std::vector<uint32_t> olen(nc), cap(nc), cidx(nc), slen(ns), sidx(ns);
     std::vector<int32_t> stat(nc);
@@ -928,6 +942,17 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
         LZ4MI_TRY(decode_launch(cb.slice(k, 1), mode, s, nullptr));
         LZ4MI_TRY(hipMemcpyAsync(&olen[k], d_out_len + k, 4, hipMemcpyDeviceToHost, s));
         LZ4MI_TRY(hipMemcpyAsync(&stat[k], d_status + k, 4, hipMemcpyDeviceToHost, s));
+        LZ4MI_TRY(hipStreamSynchronize(s));
+        // LZ4MI_LINKED_EXACT: the refused block (the one after a stored block, usually) is final now: a new
+        // linked call for the blocks behind it, whose first block rewrites over final bytes. A block that
+        // fails alone is the frame's first error: the blocks behind it keep their status and are not decoded.
+        if (!lx) continue;
+        if (stat[k] != 0) break;
+        if (k + 1 == nc) break;
+        LZ4MI_TRY(linked_launch(cb.slice(k + 1, nc - k - 1), 0, 1, s, &c->small, (uint32_t)bmax, (uint32_t)bmax));
+        ++g_linked_resumes;
+        LZ4MI_TRY(hipMemcpyAsync(&olen[k + 1], d_out_len + k + 1, 4ull * (nc - k - 1), hipMemcpyDeviceToHost, s));
+        LZ4MI_TRY(hipMemcpyAsync(&stat[k + 1], d_status + k + 1, 4ull * (nc - k - 1), hipMemcpyDeviceToHost, s));
         LZ4MI_TRY(hipStreamSynchronize(s));
     }
     // the reference's first error in block order; every compressed block but the frame's last must fill

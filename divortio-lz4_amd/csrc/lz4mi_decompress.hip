@@ -2272,8 +2272,9 @@ extern "C" hipError_t lz4mi_launch_decompress_small(const Batch& b, uint32_t x_i
 // lz4mi_linked_scratch_bytes; its first 256 bytes hold the call's state (zeroed by the caller
 // before the first window: a failure in one window fails the blocks of the later ones).
 // has_prev: the arrays hold an earlier block of the same call before this window's first.
+// f1: the reference decoder's bytes (LZ4MI_LINKED_EXACT: the rewrites in pointer form, across blocks).
 extern "C" hipError_t lz4mi_launch_decompress_linked(const Batch& b, uint32_t x_in_max, uint32_t x_out_max, void* xs,
-                                                     int force_reparse, int frame_words, int has_prev,
+                                                     int force_reparse, int frame_words, int has_prev, int f1,
                                                      hipStream_t stream) {
     if (b.nblocks == 0) return hipSuccess;
     const XLayout L = lz4mi::x_layout(b.nblocks, x_in_max, x_out_max, true);
@@ -2285,5 +2286,5 @@ extern "C" hipError_t lz4mi_launch_decompress_linked(const Batch& b, uint32_t x_
     a.in_len = L.head.in<uint32_t>(xs) + 8;
     e = parse_exported(a, L, xs, force_reparse, lz4mi::lz4mi_decompress_xl_kernel, stream);
     if (e != hipSuccess) return e;
-    return lz4mi_launch_expand(b, L, xs, true, 0, frame_words, stream);
+    return lz4mi_launch_expand(b, L, xs, true, f1, frame_words, stream);
 }

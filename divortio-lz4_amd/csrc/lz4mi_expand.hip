@@ -547,7 +547,8 @@ __global__ __launch_bounds__(kXThreads) void lz4mi_gather_kernel(ExpArgs a) { ga
 // Output races: the gather writes out[out_off[p] .. + min(out_len, out_cap)) of the exported blocks
 // with status 0; link_src classifies exactly those bytes as unresolved, so no kHist pointer names a
 // byte this window's gather writes. Stored blocks (LZ4MI_FRAME_WORDS) are copied by
-// lz4mi_linked_stored_kernel, which precedes the gather on the stream.
+// lz4mi_linked_stored_kernel, which precedes the gather on the stream; so do the bytes that
+// lz4mi_xf1ptr_linked_kernel writes below the window's first block (LZ4MI_LINKED_EXACT).
 constexpr int32_t kStCross = -9, kStArg = -101, kStRange = -8;   // include/lz4mi.h
 constexpr uint32_t kSpanMax = 1u << 30;
 
@@ -643,6 +644,101 @@ __global__ __launch_bounds__(256) void lz4mi_linked_stored_kernel(ExpArgs a, con
     }
 }
 
+// ---- linked reference mode (LZ4MI_LINKED_EXACT): the rewrites in pointer form across blocks ----
+// lz4mi_xf1ptr_kernel's pass for a linked window (DESIGN §4.8 holds the exactness argument). The
+// region [s + ml - 8, s) of a block's first sequence can start up to 4 bytes below the block; every
+// other region lies inside its block (a match writes >= 4 bytes). A region byte below the block, at
+// absolute position A, is classified as link_src classifies a source:
+//   1. inside the decoded part of an exported, status-0 earlier block p of the window: p's pointer for
+//      A becomes the pointer of A - off (a lower window index, or final history);
+//   2. anything else is final before this window runs (the caller's bytes, a gap, a stored block, a
+//      short block's unused tail): for the window's first block, whose sources are final too, out[A]
+//      is written here, before the gather and every read of it (A < 0 is dropped, a source below
+//      out[0] reads 0, as the reference's typed array does);
+//   3. otherwise the block is refused: LZ4MI_ERR_CROSS_BLOCK and the after-failure rule, so the
+//      caller can resume there. So is a block with a rewrite that would read below out[0] while a
+//      dictionary is present (the reference reads 0 there, a history pointer the dictionary).
+// Two passes of the same walk: the check (APPLY = false) runs before lz4mi_linked_fail_kernel and
+// only sets statuses, so a refused block and the blocks after it write nothing, a rewrite below
+// their own slot included; the apply runs between the linked expand and the jump rounds.
+constexpr uint32_t kFinalByte = 0xFFFFFFFFu;
+
+// The window index of the pointer of absolute position `pos` below block b's start, or kFinalByte
+// when no block of this window produces that byte (link_src's walk and condition).
+__device__ __forceinline__ uint32_t link_at(const ExpArgs& a, uint32_t b, int64_t pos) {
+    for (uint32_t p = b; p-- > 0;) {
+        const int64_t po = (int64_t)a.out_off[p];
+        if (pos < po) continue;
+        if (a.xcnt[p] != kNotExported && a.status[p] == 0 && pos - po < (int64_t)min(a.out_len[p], a.out_cap[p]))
+            return p * a.x_out_max + (uint32_t)(pos - po);
+        break;
+    }
+    return kFinalByte;
+}
+
+template <bool APPLY>
+__device__ __forceinline__ void xf1ptr_linked_body(const ExpArgs& a) {
+    const uint32_t sg = blockIdx.x, b = blockIdx.y;
+    if (a.status[b] != 0 || a.xcnt[b] == kNotExported) return;
+    const SegGeom G = seg_geom(a.in_len[b]);
+    if (sg >= G.S) return;
+    const SegRec* R = a.xrec + (size_t)b * a.nseg;
+    // (the check without a dictionary: only the block's first sequence can be refused)
+    if (!APPLY && !a.dict && R[sg].g0 != 0) return;
+    const uint32_t base = R[sg].base, send = base + R[sg].olen, cnt = R[sg].cnt;
+    const uint4* E = seg_entries(a, b, sg, G);
+    const int64_t out_off = (int64_t)a.out_off[b];
+    const int64_t n = min(a.out_len[b], a.out_cap[b]);
+    const uint32_t wb = b * a.x_out_max;
+    uint32_t* P = a.ptr + (size_t)wb;
+    bool any = false, refuse = false;
+    for (uint32_t k = threadIdx.x; k < cnt; k += kXThreads) {
+        if (!APPLY && !a.dict && k != 0) break;
+        const uint4 e = E[k];
+        const int64_t ms = (int64_t)base + e.x + e.z, off = e.w;
+        const int64_t ml = (k + 1 < cnt ? (int64_t)base + E[k + 1].x : (int64_t)send) - ms;
+        if (ml == 0 || ml >= 8 || off < 8 || out_off + ms - off < 0) continue;
+        const int64_t p0 = ms + ml - 8;
+        if (a.dict && out_off + p0 - off < 0) {
+            refuse = true;
+            continue;
+        }
+        for (int64_t q = p0; q < 0; ++q) {   // below the block: the first sequence's region only
+            const int64_t A = out_off + q, src = A - off;
+            if (A < 0) continue;
+            const uint32_t at = link_at(a, b, A);
+            if (at != kFinalByte) {
+                if (APPLY) {
+                    const uint32_t sp = link_at(a, b, src);
+                    a.ptr[at] = sp != kFinalByte ? sp : (kHist | (uint32_t)(src - (int64_t)a.win[1] + 65536));
+                    any = true;
+                }
+            } else if (b == 0) {
+                if (APPLY) a.out[A] = src >= 0 ? a.out[src] : (uint8_t)0;
+            } else {
+                refuse = true;
+            }
+        }
+        if (!APPLY) continue;
+        for (int64_t q = p0 > 0 ? p0 : 0; q < ms && q < n; ++q) {
+            const int64_t y = q - off;
+            P[q] = y >= 0 ? wb + (uint32_t)y : link_src(a, b, (int32_t)y);
+            any = true;
+        }
+    }
+    if (!APPLY) {
+        if (refuse) {
+            a.status[b] = kStCross;
+            a.out_len[b] = 0;
+        }
+        return;
+    }
+    // (a block the check refused has a status and never gets here)
+    if (__syncthreads_or(any) && threadIdx.x == 0) a.flags[0] = 1u;
+}
+__global__ __launch_bounds__(kXThreads) void lz4mi_xf1ptr_linked_check_kernel(ExpArgs a) { xf1ptr_linked_body<false>(a); }
+__global__ __launch_bounds__(kXThreads) void lz4mi_xf1ptr_linked_kernel(ExpArgs a) { xf1ptr_linked_body<true>(a); }
+
 __global__ __launch_bounds__(kXThreads) void lz4mi_expand_linked_kernel(ExpArgs a) { expand_body<true>(a); }
 __global__ __launch_bounds__(kXThreads) void lz4mi_jump_linked_kernel(ExpArgs a, int r) { jump_body<true>(a, r); }
 __global__ __launch_bounds__(kXThreads) void lz4mi_gather_linked_kernel(ExpArgs a) { gather_body<true>(a); }
@@ -699,7 +795,8 @@ static ExpArgs exp_args(const Batch& b) {
 // failing block and the stored blocks, then expand, up to kJumpRounds jump rounds (each returns at
 // once when the previous one left nothing to follow; a thread whose 16 bytes are resolved at once
 // too), chase and gather (linked: over the window's pointer array). `xs`: the pass's scratch (L).
-// f1: reference mode (small path only); frame_words: linked only.
+// f1: reference mode (linked: LZ4MI_LINKED_EXACT, the check before the failure rule and the apply
+// after the expand); frame_words: linked only.
 extern "C" hipError_t lz4mi_launch_expand(const lz4mi::Batch& b, const lz4mi::XLayout& L, void* xs, bool linked,
                                           int f1, int frame_words, hipStream_t stream) {
     using namespace lz4mi;
@@ -731,17 +828,21 @@ extern "C" hipError_t lz4mi_launch_expand(const lz4mi::Batch& b, const lz4mi::XL
     const int isolate = !linked && nblocks > 1 ? 1 : 0;
     hipError_t e = hipMemsetAsync(a.flags, 0, L.flags.bytes, stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.done, 0, L.done.bytes, stream);
-    if (e == hipSuccess && f1) e = hipMemsetAsync(redo, 0, sizeof(uint32_t) * nblocks, stream);
+    if (e == hipSuccess && f1 && !linked) e = hipMemsetAsync(redo, 0, sizeof(uint32_t) * nblocks, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(lz4mi_xbase_kernel, dim3(nblocks), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(lz4mi_xcheck_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a, isolate);
     hipLaunchKernelGGL(lz4mi_xstatus_kernel, dim3(nblocks), dim3(64), 0, stream, a);
+    if (linked && f1)   // the blocks reference mode refuses, before the failure rule
+        hipLaunchKernelGGL(lz4mi_xf1ptr_linked_check_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a);
     if (linked) hipLaunchKernelGGL(lz4mi_linked_fail_kernel, dim3(1), dim3(256), 0, stream, a, nblocks, xl);
     if (linked && frame_words)
         hipLaunchKernelGGL(lz4mi_linked_stored_kernel, dim3(64, nblocks), dim3(256), 0, stream, a, b.in_len);
     const dim3 grid(min(a.ntiles, kXGrid));
     hipLaunchKernelGGL(linked ? lz4mi_expand_linked_kernel : lz4mi_expand_kernel, grid, dim3(kXThreads), 0, stream, a);
-    if (f1)
+    if (f1 && linked)
+        hipLaunchKernelGGL(lz4mi_xf1ptr_linked_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a);
+    else if (f1)
         hipLaunchKernelGGL(lz4mi_xf1ptr_kernel, dim3(nseg, nblocks), dim3(kXThreads), 0, stream, a, isolate, redo);
     for (int r = 0; r < kJumpRounds; ++r)
         hipLaunchKernelGGL(linked ? lz4mi_jump_linked_kernel : lz4mi_jump_kernel, grid, dim3(kXThreads), 0, stream, a, r);

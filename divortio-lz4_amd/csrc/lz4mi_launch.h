@@ -83,7 +83,8 @@ hipError_t lz4mi_launch_decompress_small(const lz4mi::Batch& b, uint32_t x_in_ma
                                          int force_reparse, int f1, hipStream_t stream);
 size_t lz4mi_linked_scratch_bytes(uint32_t nblocks, uint32_t x_in_max, uint32_t x_out_max);
 hipError_t lz4mi_launch_decompress_linked(const lz4mi::Batch& b, uint32_t x_in_max, uint32_t x_out_max, void* xs,
-                                          int force_reparse, int frame_words, int has_prev, hipStream_t stream);
+                                          int force_reparse, int frame_words, int has_prev, int f1,
+                                          hipStream_t stream);
 hipError_t lz4mi_launch_linked_prep(const lz4mi::Batch& b, const lz4mi::XLayout& L, void* xs, int frame_words,
                                     int has_prev, hipStream_t stream);
 hipError_t lz4mi_launch_expand(const lz4mi::Batch& b, const lz4mi::XLayout& L, void* xs, bool linked, int f1,

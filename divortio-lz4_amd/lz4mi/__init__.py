@@ -31,6 +31,7 @@ XXH_LEN64 = 0x10
 BLOCK_CHECKSUM = 0x20
 FRAME_WORDS = 0x40
 LINKED = 0x80
+LINKED_EXACT = 0x100
 
 GEN_RANDOM, GEN_REPETITIVE, GEN_TILES216 = 0, 1, 2
 GENERATORS = {"random": GEN_RANDOM, "repetitive": GEN_REPETITIVE, "tiles216": GEN_TILES216}
@@ -285,6 +286,15 @@ def _dec_flags(js_compat, js_exact):
     return JS_COMPAT if js_compat else (JS_EXACT if js_exact else 0)
 
 
+def _linked_flag(linked):
+    """linked=True: LZ4MI_LINKED (spec mode); linked="exact": LZ4MI_LINKED_EXACT (the reference's bytes)."""
+    if isinstance(linked, str):
+        if linked != "exact":
+            raise ValueError("linked: True, False or 'exact'")
+        return LINKED_EXACT
+    return LINKED if linked else 0
+
+
 def _pack(arrs):
     n = len(arrs)
     in_len = np.array([a.size for a in arrs], dtype=np.uint32)
@@ -338,7 +348,9 @@ def decompress_blocks(blocks, out_sizes=None, js_compat=False, dictionary=None, 
     """Independent compressed blocks -> (statuses, outputs) (GPU).
     linked: the blocks may reference the output of the blocks before them (LZ4MI_LINKED: the
     blocks of a dependent frame in order; the outputs lie back to back); after the first
-    failing block every later one reports ERR_CROSS_BLOCK. Spec mode only.
+    failing block every later one reports ERR_CROSS_BLOCK. Spec mode; linked="exact"
+    (LZ4MI_LINKED_EXACT): the reference decoder's bytes, what it leaves in one array after decoding
+    the blocks in order -- its tail rewrite reaches up to 4 bytes into the block before.
     out_sizes=None: the sizes are measured first (decoded_sizes) and the blocks decoded at them;
     a block the size pass fails keeps that status and decodes to nothing.
     js_compat: the serial reference-exact kernel; js_exact: the parallel spec
@@ -369,7 +381,7 @@ def decompress_blocks(blocks, out_sizes=None, js_compat=False, dictionary=None, 
     d = _u8(dictionary)
     _check(lib().lz4mi_decompress_blocks(_p(src), _p(in_off), _p(in_len), _p(out), _p(out_off), _p(out_cap),
                                          _p(d), 0 if d is None else d.size, _p(out_len), _p(status), n,
-                                         _dec_flags(js_compat, js_exact) | (LINKED if linked else 0), None))
+                                         _dec_flags(js_compat, js_exact) | _linked_flag(linked), None))
     outs = [out[int(o):int(o) + min(int(l), int(c))].copy() for o, l, c in zip(out_off, out_len, out_cap)]
     return status, outs, out_len
 
@@ -420,11 +432,11 @@ def decompress_blocks_dev(in_ptr, in_off_ptr, in_len_ptr, out_ptr, out_off_ptr, 
     """Batch decode on device pointers. frame_words: in_len holds frame size words (bit 31 =
     stored block, copied in the same launch; include/lz4mi.h LZ4MI_FRAME_WORDS). js_exact: the
     reference decoder's bytes (LZ4MI_JS_EXACT, the JS layer's default). linked: dependent blocks
-    in ascending, disjoint slots (LZ4MI_LINKED, spec mode)."""
+    in ascending, disjoint slots (LZ4MI_LINKED, spec mode; "exact": LZ4MI_LINKED_EXACT, the reference's bytes)."""
     _check(lib().lz4mi_decompress_blocks(in_ptr, in_off_ptr, in_len_ptr, out_ptr, out_off_ptr, out_cap_ptr,
                                          dict_ptr, dict_len, out_len_ptr, status_ptr, nblocks,
                                          DEVICE_PTRS | _dec_flags(js_compat, js_exact) |
-                                         (FRAME_WORDS if frame_words else 0) | (LINKED if linked else 0),
+                                         (FRAME_WORDS if frame_words else 0) | _linked_flag(linked),
                                          stream or None))
 
 
@@ -448,10 +460,11 @@ def xxh32_blocks_dev(in_ptr, off_ptr, len_ptr, hashes_ptr, nblocks, seed=0, stre
 def frame_decompress_dev(frame_ptr, frame_len, out_ptr, out_cap, stream=0, js_exact=False, linked=False):
     """Decode a device-resident LZ4 frame into out (device pointers): returns the info dict
     (include/lz4mi.h lz4mi_frame_decompress); raises if the frame needs the host path.
-    linked: the compressed blocks go in one linked call (LZ4MI_LINKED, not with js_exact)."""
+    linked: the compressed blocks go in one linked call (LZ4MI_LINKED, not with js_exact; "exact":
+    LZ4MI_LINKED_EXACT, that call in the reference decoder's bytes)."""
     info = np.zeros(8, dtype=np.int64)
     _check(lib().lz4mi_frame_decompress(frame_ptr, frame_len, out_ptr, out_cap, info.ctypes.data,
-                                        DEVICE_PTRS | (JS_EXACT if js_exact else 0) | (LINKED if linked else 0),
+                                        DEVICE_PTRS | (JS_EXACT if js_exact else 0) | _linked_flag(linked),
                                         stream or None))
     keys = ("status", "flg", "content_size", "written", "stored_blocks", "checksum_pos", "block_max", "overflow")
     return dict(zip(keys, (int(x) for x in info)))

@@ -932,6 +932,9 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
     (LZ4MI_LINKED): the layout route passes the flag, and a frame the layout walk declines takes
     the route "linked" whatever FLG 0x20 says -- the measured route with one linked batch; the
     host route stays the last resort (the empty frame, frames with an error in a block).
+    linked="exact" (with or without js_exact): the reference decoder's bytes with the layout route
+    passing LZ4MI_LINKED_EXACT, one linked call for a dependent frame with a content size; a frame
+    the layout walk declines takes the routes js_exact=True has without `linked`.
     The content checksum (FLG 0x04) is verified on the host, streamed piece by piece. Returns
     the content as a uint8 CUDA tensor: with a content size that many bytes, zeros behind what
     the blocks wrote (the reference's zero-initialised result). Raises lz4mi.Lz4miError with the
@@ -939,6 +942,11 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
     is ERR_RANGE before anything is allocated for it."""
     import torch
     import lz4mi
+    lx = isinstance(linked, str) and linked == "exact"
+    if isinstance(linked, str) and not lx:
+        raise ValueError("linked: True, False or 'exact'")
+    if lx:
+        js_exact = True                            # (every other route: the ones js_exact=True has)
     # the library binds one device per process: a frame on another device raises ERR_ARG here
     lz4mi.init(frame.device.index if frame.device.index is not None else torch.cuda.current_device())
     s = stream if stream is not None else torch.cuda.current_stream(frame.device)
@@ -965,7 +973,7 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
             raise lz4mi.Lz4miError(lz4mi.ERR_ARG)   # the size field itself is cut: the host route's frame
         out = torch.empty(max(1, size), dtype=torch.uint8, device=frame.device)
         info = lz4mi.frame_decompress_dev(frame.data_ptr(), frame.numel(), out.data_ptr(), size, s.cuda_stream,
-                                          js_exact=js_exact, linked=lk)
+                                          js_exact=js_exact and not lx, linked="exact" if lx else lk)
     except lz4mi.Lz4miError as e:
         if e.status != lz4mi.ERR_ARG:
             raise

@@ -74,7 +74,12 @@ extern "C" {
                                     they exceed out_cap[b], the reference's result.set RangeError) */
 #define LZ4MI_LINKED 0x80u       /* lz4mi_decompress_blocks, lz4mi_frame_decompress (spec mode): the blocks may
                                     reference the output of the blocks before them (dependent-block frames);
-                                    the whole batch is decoded in one call. Contract: lz4mi_decompress_blocks. */
+                                    the whole batch is decoded in one call. Contract: lz4mi_decompress_blocks.
+                                    The reference decoder's bytes for such a batch: LZ4MI_LINKED_EXACT. */
+#define LZ4MI_LINKED_EXACT 0x100u /* lz4mi_decompress_blocks, lz4mi_frame_decompress: LZ4MI_LINKED with the result
+                                    of the reference decoder run on the blocks in order on one array, its
+                                    double-copy-tail rewrite (F1) across block boundaries included. Implies
+                                    LZ4MI_LINKED. Contract: lz4mi_decompress_blocks. */
 
 /* Largest block the kernels accept (the reference's largest block size is 4 MiB;
  * raw calls may pass more, up to 2^31-1 like the reference's `|0` arithmetic). */
@@ -113,7 +118,8 @@ const char* lz4mi_build_id(void);
  * in order on one lane with the reference's byte-level behaviour.
  * Returns LZ4MI_OK when the batch ran (per-block errors are in status[]).
  *
- * LZ4MI_LINKED (spec mode; with LZ4MI_JS_COMPAT or LZ4MI_JS_EXACT: LZ4MI_ERR_ARG): dependent blocks
+ * LZ4MI_LINKED (spec mode; with LZ4MI_JS_COMPAT or LZ4MI_JS_EXACT: LZ4MI_ERR_ARG; the reference
+ * decoder's bytes: LZ4MI_LINKED_EXACT, below): dependent blocks
  * in one call. Precondition: the output slots are ascending and disjoint, out_off[b] + out_cap[b]
  * <= out_off[b+1]; gaps are allowed, the caller's bytes there are final. Result: the bytes,
  * out_len[] and status[] that nblocks successive nblocks == 1 calls in index order on the same
@@ -133,6 +139,24 @@ const char* lz4mi_build_id(void);
  * stored block is copied in the same call before anything reads it. Any nblocks: the call cuts the
  * batch into passes in index order on the one stream, as many blocks each as the scratch cap
  * (LZ4MI_SMALL_SCRATCH_MB, compared with the real allocation) and the pointer encodings allow.
+ *
+ * LZ4MI_LINKED_EXACT (implies LZ4MI_LINKED, setting both changes nothing; with LZ4MI_JS_COMPAT or
+ * LZ4MI_JS_EXACT: LZ4MI_ERR_ARG): a linked batch in the reference decoder's bytes. Result: the bytes,
+ * out_len[] and status[] of nblocks successive one-block LZ4MI_JS_EXACT calls in index order on the
+ * caller's array. The reference's tail rewrite of a match at absolute position s with offset >= 8 and
+ * length ml < 8 (blockDecompress.js:219-250) sets out[p] = out[p - off] for p in [s + ml - 8, s); at a
+ * block's first sequence with fewer than 8 - ml literals that region lies below the block's own start,
+ * in the tail of the block before it or in the caller's bytes, and is rewritten there (host pointers:
+ * the up to 8 bytes below every decoded block are copied back with it). LZ4MI_LINKED's rules for
+ * slots, the 4 MiB limits, LZ4MI_FRAME_WORDS, passes and failures hold; the first failing block and
+ * every block after it write nothing, a rewrite below their own slot included. Refusal: a block
+ * whose region below its start touches a byte that is not the decoded output of an earlier block of
+ * the same pass (a gap, a stored block, the unused tail of a short slot) while the block is not the
+ * first of its pass, or whose rewrite would read below out[0] with a dictionary present, gets
+ * LZ4MI_ERR_CROSS_BLOCK and the after-failure rule applies: decode that block alone with
+ * LZ4MI_JS_EXACT and issue a new call for the blocks after it (lz4mi_frame_decompress does). A region
+ * inside earlier blocks' decoded output, and the first block of the call (over the caller's bytes;
+ * positions below out[0] are not written and read as 0), always decode in the call.
  */
 int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
                                 uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
@@ -256,6 +280,9 @@ int32_t lz4mi_frame_pack(const uint8_t* raw, const uint64_t* raw_off, const uint
  * | LZ4MI_LINKED (spec mode only, with LZ4MI_JS_EXACT: LZ4MI_ERR_ARG): the compressed blocks are
  * issued as one linked batch after the stored copies, so a dependent-block frame needs no launch
  * per block; without it dependent blocks are decoded one per launch, in order.
+ * | LZ4MI_LINKED_EXACT (not with LZ4MI_JS_EXACT: LZ4MI_ERR_ARG): the same in the reference decoder's
+ * bytes; a block the linked call refuses (the one after a stored block, usually) is decoded alone in
+ * reference mode and the blocks after it go into a new linked call.
  * Synchronous (reads the header and the block lists back). Returns LZ4MI_ERR_ARG for frames
  * this path does not take (no content size, a block layout other than the reference encoder's,
  * out_cap too small): decode those with the host-buffer path block by block.
