@@ -21,6 +21,10 @@ __device__ void decode_block_jscompat(const DecArgs& a, uint32_t b) {
     const int64_t dlen = a.dict ? a.dict_len : 0;
     int64_t ip = 0, op = oo;
     int32_t st = 0;
+    // a rewrite reaches at most 4 bytes below the block (start + ml - 8 >= oo - 4): a failing block
+    // writes inside its own slot only, so those are put back when it fails
+    uint8_t below[4];
+    for (int k = 0; k < 4; ++k) below[k] = oo - 4 + k >= 0 ? out[oo - 4 + k] : 0;
     auto inb = [&](int64_t i) -> uint32_t { return (i >= 0 && i < iend) ? in[i] : 0u; };
     while (ip < iend) {
         uint32_t tok = inb(ip++);
@@ -66,6 +70,9 @@ __device__ void decode_block_jscompat(const DecArgs& a, uint32_t b) {
             }
         }
     }
+    if (st)
+        for (int k = 0; k < 4; ++k)
+            if (oo - 4 + k >= 0) out[oo - 4 + k] = below[k];
     a.status[b] = st;
     a.out_len[b] = st ? 0u : (uint32_t)(op - oo);
 }

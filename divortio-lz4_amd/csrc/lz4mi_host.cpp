@@ -254,10 +254,10 @@ int64_t decompress_block(Arr in, int64_t in_pos, int64_t in_end, OutArr out, int
                 if (out_pos < end) {
                     if (spec) {
                         for (; out_pos < end; ++out_pos, ++r) o[out_pos] = o[r];
-                    } else if (end - 8 >= 0) {                      // F1: the last 8 bytes again
+                    } else if (src + ml - 8 >= 0) {                 // F1: the last 8 bytes again
                         std::memcpy(o + end - 8, o + r + (end - out_pos) - 8, 8);
                         out_pos = end;
-                    } else {
+                    } else {                                        // its source starts below out[0]: those read 0
                         const int64_t t_out = end - 8, t_src = r + (end - out_pos) - 8;
                         for (int k = 0; k < 8; ++k) out.put(t_out + k, out.at(t_src + k));
                         out_pos = end;

@@ -117,6 +117,14 @@ const char* lz4mi_build_id(void);
  * then `dict`, exactly as the reference). LZ4MI_JS_COMPAT decodes the blocks
  * in order on one lane with the reference's byte-level behaviour.
  * Returns LZ4MI_OK when the batch ran (per-block errors are in status[]).
+ * Footprint (tests/test_gpu_footprint.py): a block with status 0 writes out[out_off[b] .. +min(out_len[b],
+ * out_cap[b])) and nothing else -- the rest of its slot, the bytes around it, `in`, and the entries of
+ * out_len[] / status[] from nblocks on stay the caller's; a match that is the block's last sequence is
+ * clipped at the capacity like a store to a typed array and gives status 0 with out_len[b] > out_cap[b].
+ * Only a lone block (nblocks == 1) in a reference mode also rewrites up to 4 bytes below its slot (the
+ * reference's tail rewrite of its first sequence), and LZ4MI_LINKED_EXACT as described below. A block
+ * with status != 0 has out_len[b] = 0 and may have written inside its own slot only (not the
+ * reference's partial output); a stored block that does not fit (LZ4MI_ERR_RANGE) writes nothing.
  *
  * LZ4MI_LINKED (spec mode; with LZ4MI_JS_COMPAT or LZ4MI_JS_EXACT: LZ4MI_ERR_ARG; the reference
  * decoder's bytes: LZ4MI_LINKED_EXACT, below): dependent blocks
@@ -195,6 +203,8 @@ int32_t lz4mi_decoded_sizes(const uint8_t* in, const uint64_t* in_off, const uin
  *           blockIndependence=true. Output is byte-identical to the reference encoder.
  * Block b compresses in[in_off[b] .. +in_len[b]) into out[out_off[b] ..), a slot of
  * at least lz4mi_compress_bound(in_len[b]) bytes; out_len[b] = compressed size.
+ * Footprint (tests/test_gpu_footprint.py): only out[out_off[b] .. +out_len[b]) and out_len[0 .. nblocks)
+ * are written; the rest of a slot, up to its bound, stays the caller's.
  * The stored-block decision (bufferCompress.js:221-231) is the caller's.
  */
 int32_t lz4mi_compress_blocks(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
