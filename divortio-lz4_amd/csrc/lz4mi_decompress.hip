@@ -4,23 +4,25 @@
 // batches of independent blocks. Semantics follow the reference exactly for
 // spec-valid input (positions absolute in `out`, dictionary below out[0],
 // clipped match writes, the four error strings). The reference's double-copy-
-// tail rewrite is reproduced by LZ4MI_JS_EXACT (this kernel plus
-// the in-chunk replay, f1_fixup) and by LZ4MI_JS_COMPAT (the blocks in order on
-// one lane, lz4mi_decompress_serial.hip).
+// tail rewrite is reproduced in reference mode, LZ4MI_JS_EXACT, by
+// this kernel (DecArgs::f1check: the in-chunk replay, step 7) -- batches here,
+// small batches through the export path (lz4mi_expand.hip), whose blocks with a
+// rewrite come back here (DecArgs::redo). Only LZ4MI_JS_COMPAT still decodes the
+// blocks in order on one lane (lz4mi_decompress_serial.hip).
 //
 // One wave64 per block, all 4096 blocks of a batch resident at once
-// (< 10 KiB LDS, <= 128 VGPRs -> 16 waves per CU). Per 1 KiB chunk of the
-// compressed stream:
+// (< 10 KiB LDS, <= 128 VGPRs -> 16 waves per CU). decompress_block calls the
+// steps below in this order, per 1 KiB chunk of the compressed stream:
 //  1. Stage it (+64 B lookahead) in LDS.
 //  2. next(p) of every position, branch-free (length fields of one extension
 //     byte; longer ones through a ballot-gated exact loop) into an LDS table.
-//  3. Speculative walks: lane l walks next() from 256 bytes before its 16-byte
+//  3. Speculative walks: lane l walks next() from kWarm = 512 bytes before its 16-byte
 //     segment and records the tokens it visits in the segment; LZ4 token
 //     chains resynchronise within a few steps, so walks are almost always on
 //     the true chain. Certification left to right by ballot: the first lane
 //     whose left neighbour's exit is not on its walk re-walks from it (its
 //     neighbour is settled). The result is the exact serial parse. Walks
-//     start 256 bytes back: inside long literal runs a walk can take a while
+//     start that far back: inside long literal runs a walk can take a while
 //     to fall onto the true chain, and every unsettled lane costs a pass.
 //  4. Sequence table in LDS, built sequence-major: the lanes list their tokens'
 //     positions compactly (lane l's at base(l) + j), then lane l of row i takes
@@ -28,7 +30,16 @@
 //     its output start from a row prefix sum plus the carry of the rows before
 //     and writes its entry once. Errors in the reference's order: a 32-bit test
 //     per row pair, the exact checks only from the first flagged pair on.
-//  5. Output, sequence-parallel (lane l takes sequence 64i+l), every run
+//     A true token whose match length field runs past one extension byte sends
+//     the chunk back to step 2 for the exact table (once).
+//  5. A sequence whose parse leaves the staged window (long literal runs or
+//     length varints: incompressible or highly repetitive data) is parsed from
+//     global memory with wave-wide 255-run scans. It is written after step 6 by
+//     the whole wave, literal run first, then (after it is stored, and after
+//     step 7) the match run.
+//     (Export, XP: the sequences of steps 4 and 5 go to the segment's list
+//     instead, and the chunk ends here.)
+//  6. Output, sequence-parallel (lane l takes sequence 64i+l), every run
 //     written with exact-width unaligned 16/8/4/2/1-byte pieces (the last
 //     16-byte piece of a run overlaps its predecessor instead of spilling),
 //     so lanes never touch each other's bytes:
@@ -41,11 +52,9 @@
 //     the output (L2, bypassing L1); an overlapping match (offset < length)
 //     is read through its period: a 16-byte window that wraps is merged from
 //     two loads, periods under 16 bytes are expanded in registers. Runs
-//     longer than 128 bytes are written by the whole wave.
-//  6. A sequence whose parse leaves the staged window (long literal runs or
-//     length varints: incompressible or highly repetitive data) is parsed from
-//     global memory with wave-wide 255-run scans and written by the whole
-//     wave, literal run first, then (after it is stored) the match run.
+//     longer than kLaneBytes are written by the whole wave.
+//  7. Reference mode: the chunk's matches replayed with the reference's tail
+//     rewrite where it would change a byte (f1_table, f1_fixup).
 #include "../../include/lz4mi.h"
 #include "lz4mi_common.h"
 #include "lz4mi_decompress.h"
@@ -107,14 +116,20 @@ __device__ unsigned int g_tl_id[2 * kTlMax];      // per block: HW_ID (wave, SIM
 
 #if LZ4MI_PROFILE
 __device__ unsigned long long g_prof[24];
+// A wave's accumulator: decompress_block owns it and hands it to the phases (`prof`).
+struct Prof {
+    uint64_t acc[24];
+    uint64_t t;
+};
 #define PROF(i)                              \
     do {                                     \
         const uint64_t t_ = wall_clock64();  \
-        prof[i] += t_ - prof_t;              \
-        prof_t = t_;                         \
+        prof.acc[i] += t_ - prof.t;          \
+        prof.t = t_;                         \
     } while (0)
-#define PROF_COUNT(i, n) (prof[i] += (n))
+#define PROF_COUNT(i, n) (prof.acc[i] += (n))
 #else
+struct Prof {};
 #define PROF(i) ((void)0)
 #define PROF_COUNT(i, n) ((void)0)
 #endif
@@ -1090,7 +1105,8 @@ __device__ __forceinline__ uint32_t f1_changes(const Ctx& c, int32_t ms, int32_t
 // (periodic copy: its source bytes before its start are final when it runs), and every
 // rewrite is applied (blockDecompress.js:219-250: out[p] = out[p - off] for
 // p in [ms + ml - 8, ms), after the copy). Later chunks then read the fixed output.
-__device__ void f1_fixup(const Ctx c, const DecShared& S, int lane, uint32_t nseq, bool cut, int64_t cut_ms,
+// (a call, never inlined: it is rare, and its registers are not the chunk loop's)
+__device__ __noinline__ void f1_fixup(const Ctx c, const DecShared& S, int lane, uint32_t nseq, bool cut, int64_t cut_ms,
                          int32_t coff, int32_t cml) {
     int64_t lo = INT64_MAX;
     const uint32_t n = nseq + (cut ? 1u : 0u);
@@ -1137,104 +1153,83 @@ __device__ void f1_fixup(const Ctx c, const DecShared& S, int lane, uint32_t nse
     }
 }
 
-// LK (with XP): a linked window (LZ4MI_LINKED, lz4mi_expand.hip): every block left exported by
+// ---------------------------------------------------------------- the block
+// A frame's stored block (bufferDecompress.js:173-180): its bytes, in this launch, paced
+// like any long literal run; larger than the slot: the reference's RangeError.
+__device__ __forceinline__ void stored_block(const DecArgs& a, const Ctx& c, uint32_t b, uint32_t out_cap, int lane) {
+    int32_t status = 0;
+    const int32_t n = c.in_len;
+    if ((uint32_t)n > out_cap) {
+        status = LZ4MI_ERR_RANGE_STATUS;
+    } else if (n >= 16) {
+        long_literals(c.dst, c.blk, n, lane);
+    } else if (lane < n) {
+        c.dst[lane] = c.blk[lane];
+    }
+    if (lane == 0) {
+        a.status[b] = status;
+        a.out_len[b] = status ? 0u : (uint32_t)n;
+    }
+}
+
+// ---------------------------------------------------------------- export (XP)
+// Small-batch export (lz4mi_expand.hip): a wave per segment of the block, which parses its
+// segment and exports the sequences instead of writing them. All of it uniform.
+struct XState {
+    bool on = false;                    // this block is exported (else: one wave decodes it as usual)
+    uint4* xs = nullptr;                // the segment's exported sequences
+    SegRec* xr = nullptr;               // its record
+    uint32_t seg_lo = 0, seg_hi = 0;    // the segment: tokens in [seg_lo, seg_hi)
+    // the entry found, done, the speculation failed, entry / exit tokens, sequences exported,
+    // their output bytes, the first parse error; OG: output position of the entry in this
+    // wave's running count; pass 1 / 2: the re-parse from `entry` of phase 1 (exact) / 2
+    bool started = false, done = false, fail = false;
+    uint32_t G = 0, X = 0, nx = 0, olen = 0, err = 0xFFFFFFFFu, entry = 0;
+    int64_t OG = 0;
+    int pass = 0, restart = 0;
+};
+
+// Does this wave (segment sg of block wblk, phase a.xphase) parse at all? Sets x.on, the
+// segment, the pass and c.ip, where its parse starts.
+// LK: a linked window (LZ4MI_LINKED, lz4mi_expand.hip): every block left exported by
 // lz4mi_linked_prep_kernel is within the export limits and is parsed for export whatever its ratio --
 // a one-wave decode would write `out` and read predecessors the gather has not written yet.
-template <bool XP, bool LK = false>
-__device__ __forceinline__ void decompress_block(const DecArgs& a) {
-    __shared__ DecShared S;
-    const int lane = threadIdx.x;
-    const uint32_t nseg = XP ? a.xsegs : 1u;   // XP: waves per block (one per segment)
-    if (blockIdx.x >= a.nblocks * nseg) return;
-    const uint32_t wblk = XP ? blockIdx.x / nseg : blockIdx.x;   // (XP: block-major, segments of a block on
-    const uint32_t sg = XP ? blockIdx.x - wblk * nseg : 0u;       //  consecutive CUs, every XCD)
-    if (LK && uniform(a.xcnt[wblk]) == kNotExported) return;     // stored, refused or after a failure: not parsed
-    const uint32_t b = a.order ? uniform(a.order[wblk]) : wblk;
-    if (!XP && a.redo && !uniform(a.redo[b])) return;   // (small batches, reference mode: the blocks to redo)
-#if LZ4MI_TIMELINE
-    const uint64_t tl_t0 = wall_clock64();
-#endif
-
-    // the block's scalars in SGPRs (readfirstlane): as VGPRs the compiler would keep
-    // per-lane copies of values derived from them and spill those to scratch
-    const uint64_t in_off = uniform64(a.in_off[b]), out_off = uniform64(a.out_off[b]);
-    const uint32_t out_cap = uniform(a.out_cap[b]);
-    Ctx c;
-    c.blk = a.in + in_off;
-    const uint32_t word = uniform(a.in_len[b]);
-    c.in_len = (int32_t)(a.frame_words ? word & 0x7FFFFFFFu : word);
-    c.out_off = (int64_t)out_off;
-    c.dst = a.out + out_off;
-    c.cap = out_cap > 0x7FFFFFFFu ? 0x7FFFFFFF : (int32_t)out_cap;
-    c.dict = a.dict;
-    c.dict_len = a.dict ? (int32_t)a.dict_len : 0;
-    c.isolate = a.isolate;
-    c.ip = 0;
-    c.O = 0;
-    int32_t status = 0;
-    if (a.frame_words && (word & 0x80000000u)) {
-        // a frame's stored block (bufferDecompress.js:173-180): its bytes, in this launch, paced
-        // like any long literal run; larger than the slot: the reference's RangeError
-        const int32_t n = c.in_len;
-        if ((uint32_t)n > out_cap) {
-            status = LZ4MI_ERR_RANGE_STATUS;
-        } else if (n >= 16) {
-            long_literals(c.dst, c.blk, n, lane);
-        } else if (lane < n) {
-            c.dst[lane] = c.blk[lane];
-        }
-        if (lane == 0) {
-            a.status[b] = status;
-            a.out_len[b] = status ? 0u : (uint32_t)n;
-        }
-        return;
-    }
-    // small-batch export (XP, lz4mi_expand.hip): segment sg of the block, parsed only
+template <bool LK>
+__device__ __forceinline__ bool x_enter(const DecArgs& a, Ctx& c, XState& x, int lane, uint32_t wblk, uint32_t sg,
+                                        uint32_t nseg, uint32_t out_cap) {
     // (a block of long runs -- output over 32x its compressed size: repetitive data, one periodic
     // match -- decodes faster in one wave, as in the batch kernel: 1.1 ms for 4 MiB at any batch
     // size, against 0.77 ms alone / 1.57 ms for 16 through the pointers, profiles/r06c)
-    const bool xp = XP && (LK || ((uint32_t)c.in_len <= a.x_in_max && out_cap <= a.x_out_max &&
-                                  (uint64_t)out_cap < (uint64_t)c.in_len * kXRatioMax &&
-                                  !(a.x_flat1 && (uint64_t)c.in_len * 16 >= (uint64_t)out_cap * 15)));
+    x.on = LK || ((uint32_t)c.in_len <= a.x_in_max && out_cap <= a.x_out_max &&
+                  (uint64_t)out_cap < (uint64_t)c.in_len * kXRatioMax &&
+                  !(a.x_flat1 && (uint64_t)c.in_len * 16 >= (uint64_t)out_cap * 15));
     // past the export limits (or ratio >= 32): one wave decodes the block as usual -- segment
     // b mod 256, i.e. workgroup 257 b (mod 256 CUs: a CU of its own for every block, where
     // segment 0 would put the blocks of a batch on one CU)
-    if (XP && !xp && (a.xphase != 0 || sg != wblk % nseg)) return;
-    uint4* xs = nullptr;
-    SegRec* xr = nullptr;
-    uint32_t seg_lo = 0, seg_hi = 0;    // the segment: tokens in [seg_lo, seg_hi)
-    if (XP && xp) {
-        const SegGeom G = seg_geom((uint32_t)c.in_len);   // S segments of ~kSegTarget bytes
-        if (sg >= G.S) return;
-        seg_lo = sg * G.L;
-        seg_hi = sg + 1 == G.S ? (uint32_t)c.in_len : min((uint32_t)c.in_len, seg_lo + G.L);
-        xs = a.xseq + (size_t)wblk * a.xseq_stride + (size_t)sg * G.stride;
-        xr = a.xrec + (size_t)wblk * nseg + sg;
-    }
-    if (XP && a.xphase != 0 && !xp) return;
-    // export state (uniform): the entry found, done, the speculation failed, entry / exit tokens,
-    // sequences exported, their output bytes, the first parse error; x_OG: output position of
-    // the entry in this wave's running count; pass 1: the exact re-parse from x_entry
-    bool x_started = false, x_done = false, x_fail = false;
-    uint32_t x_G = 0, x_X = 0, nx = 0, x_olen = 0, x_err = 0xFFFFFFFFu, x_entry = 0;
-    int64_t x_OG = 0;
-    int x_pass = 0, x_restart = 0;
-    if (XP && xp && a.xphase == 2) {
+    if (!x.on) return a.xphase == 0 && sg == wblk % nseg;
+    const SegGeom G = seg_geom((uint32_t)c.in_len);   // S segments of ~kSegTarget bytes
+    if (sg >= G.S) return false;
+    x.seg_lo = sg * G.L;
+    x.seg_hi = sg + 1 == G.S ? (uint32_t)c.in_len : min((uint32_t)c.in_len, x.seg_lo + G.L);
+    x.xs = a.xseq + (size_t)wblk * a.xseq_stride + (size_t)sg * G.stride;
+    x.xr = a.xrec + (size_t)wblk * nseg + sg;
+    SegRec* const xr = x.xr;
+    if (a.xphase == 2) {
         // phase 2: every segment whose guess disagrees with the previous one's exit, re-parsed
         // from that exit at once (lz4mi_xverify_kernel's `from`), a guess again -- the check then
         // runs again: a wrong guess does not make the later guesses wrong, and the segments
         // before a wrong one are mostly right (text, ~10 % of ~190 segments: chained one after
         // another in phase 1, 2.1 ms for a block)
         const uint32_t from = uniform(xr->from);
-        if (from == kNoBase) return;
-        x_pass = 2;
-        x_entry = from;
+        if (from == kNoBase) return false;
+        x.pass = 2;
+        x.entry = from;
     }
-    if (XP && xp && a.xphase == 1) {
+    if (a.xphase == 1) {
         // phase 1: segments from the first wrong entry on, in order: re-parse from the previous
         // segment's final exit unless the speculative entry equals it
         const uint32_t sstar = a.xfirst[wblk];
-        if (sg < sstar) return;
+        if (sg < sstar) return false;
         uint32_t fp = 0;
         if (sg == sstar) {
             fp = xr[-1].exit;                    // final: accepted by lz4mi_xverify_kernel
@@ -1251,7 +1246,7 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
         if (fp == kFinErr) {                     // after the block's first error: nothing here
             fin = kFinErr;
             if (lane == 0) { xr->cnt = 0; xr->olen = 0; xr->err = 0xFFFFFFFFu; }
-        } else if (fp >= seg_hi) {               // the chain passes over the segment
+        } else if (fp >= x.seg_hi) {             // the chain passes over the segment
             fin = fp;
             if (lane == 0) { xr->entry = xr->exit = fp; xr->cnt = 0; xr->olen = 0; xr->err = 0xFFFFFFFFu; }
         } else if (sg != sstar && !xr->fail && xr->entry == fp) {
@@ -1261,686 +1256,833 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
         }
         if (!reparse) {
             if (lane == 0) __hip_atomic_store(&xr->fin, fin + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            return;
+            return false;
         }
-        x_pass = 1;
-        x_entry = fp;
+        x.pass = 1;
+        x.entry = fp;
     }
+    // a guess: from kSegWarm before the segment, on whatever chain the walk falls onto
+    c.ip = x.pass ? (int32_t)x.entry
+                  : (x.seg_lo >= (uint32_t)c.in_len ? c.in_len : (int32_t)(x.seg_lo - min(x.seg_lo, kSegWarm)));
+    return true;
+}
+
+// ---------------------------------------------------------------- 1. staging
+// The 16-byte pieces of [at, at + kLim), two per lane (unaligned loads).
+__device__ __forceinline__ void stage_loads(const Ctx& c, int64_t at, int lane, uint4& p0, uint4& p1) {
+    p0 = stage_piece(c, at + 16 * opaque(lane));
+    if (lane < kStageWords / 4 - kWave) p1 = stage_piece(c, at + 16 * (kWave + opaque(lane)));
+}
+__device__ __forceinline__ void stage_write(DecShared& S, int lane, const uint4& p0, const uint4& p1) {
+    __builtin_memcpy((uint8_t*)S.stage + 16 * lane, &p0, 16);
+    if (lane < kStageWords / 4 - kWave) __builtin_memcpy((uint8_t*)S.stage + 16 * (kWave + lane), &p1, 16);
+}
+
+// The next chunk's staged bytes, loaded early: during this chunk's table build or, after a
+// cut sequence, ahead of this chunk's stores.
+struct Prefetch {
+    uint4 pf0 = make_uint4(0, 0, 0, 0), pf1 = make_uint4(0, 0, 0, 0);
+    int64_t pf_at = -1;     // compressed position pf0/pf1 were loaded from
+    bool have_pf = false;
+};
+__device__ __forceinline__ void prefetch(const Ctx& c, Prefetch& pf, int64_t at, int lane) {
+    stage_loads(c, at, lane, pf.pf0, pf.pf1);
+    pf.pf_at = at;
+    pf.have_pf = true;
+}
+// Explicitly waited for (wait_vmem): the next chunk's stage does not wait for this chunk's stores.
+__device__ __forceinline__ void settle(Prefetch& pf) {
+    settle(pf.pf0);
+    settle(pf.pf1);
+}
+
+// Stage [ip, ip + kLim), from the prefetch when it was loaded from ip.
+// (each branch writes the stage itself: a write after the join would wait for the
+// fresh loads of the first branch on both, i.e. for every store still in flight)
+__device__ __forceinline__ void stage_chunk(const Ctx& c, DecShared& S, Prefetch& pf, int lane) {
+    if (!pf.have_pf || pf.pf_at != c.ip) {
+        uint4 p0, p1 = make_uint4(0, 0, 0, 0);
+        stage_loads(c, (int64_t)c.ip, lane, p0, p1);
+        stage_write(S, lane, p0, p1);
+    } else {
+        stage_write(S, lane, pf.pf0, pf.pf1);
+    }
+    pf.have_pf = false;
+    __syncthreads();
+}
+
+// ---------------------------------------------------------------- 2, 3. chunk parse
+// The exact serial parse of the staged chunk: lane l's tokens in [16 l, 16 l + 16) as the bits
+// of `vis`; where the chain leaves the chunk (`tail`: chunk-relative, kEnd or kStop); the last
+// token starting in the chunk and its lane; `cut`: that token's sequence leaves the staged
+// window (tail == kStop) and is parsed from memory (cut_seq).
+struct Parse {
+    uint32_t vis, tail, last_tok;
+    int last_lane;
+    bool cut;
+};
+__device__ __forceinline__ Parse parse_chunk(DecShared& S, int lane, uint32_t rem, bool fast_tab, Prof& prof) {
+    const uint8_t* s = (const uint8_t*)S.stage;
+    const uint32_t seg0 = 16u * lane, seg1 = seg0 + 16;
+    uint32_t vis, tail;
+    PROF(0);
+    // Wave priorities by phase (the 4 waves of a SIMD are in different phases):
+    // output rounds 3 > walks 1 > next-token table 0. The copies' loads and
+    // stores go out first and the LDS-bound parse fills the gaps: tiles216 -0.9 %,
+    // mix -2.5 %, copy -1.5 % (A/B in one process, profiles/r02j/prio_ab.json).
+    __builtin_amdgcn_s_setprio(0);
+    // ---- 2. next-token table -----------------------------------------
+    // Away from the block's end (fast_tab) four positions per lane from two stage
+    // dwords, assuming length fields of at most one extension byte: a token whose
+    // literal field runs on (b1 == 255) stops the chain (the cut path parses it), and
+    // a match field that runs on (checked on the true tokens in the table build) sends
+    // the chunk back here for the exact table. Near the end: the exact table.
+    uint16_t* nxt = S.nxt;
+    if (fast_tab) {
+        next_table_fast(S.stage, nxt, lane);
+    } else {   // all positions' fields read at once; the rare longer length fields afterwards
+        static_assert(kChunk % kWave == 0, "whole rows per lane");
+        uint32_t slm = 0;
+#pragma unroll
+        for (int i = 0; i < kChunk / kWave; ++i) {
+            bool slow;
+            const uint32_t v = next_fast(s, lane + kWave * i, rem, slow);
+            slm |= (slow ? 1u : 0u) << i;
+            nxt[lane + kWave * i] = enc_next(v);
+        }
+        if (__ballot(slm != 0)) {
+            for (uint32_t m = slm; m; m &= m - 1) {
+                const uint32_t p = lane + kWave * __builtin_ctz(m);
+                nxt[p] = enc_next(next_token(s, p, rem));
+            }
+        }
+    }
+    __syncthreads();
+    // 2- and 4-step jumps (the warm-up walks only need where the chain lands)
+    jump_table(nxt, S.nxt2, lane);
+    __syncthreads();
+    jump_table(S.nxt2, S.nxt4, lane);
+    __syncthreads();
+#if LZ4MI_ABLATE == 3
+    return Parse{0u, (uint32_t)kChunk, 0u, 0, false};   // (the chunk loop steps by kChunk)
+#endif
+
+    PROF(1);
+    __builtin_amdgcn_s_setprio(1);
+    // ---- 3. speculative walks + certification -------------------------
+    uint32_t x;
+    vis = 0;
+    {   // warm-up walk; lanes whose warm-up would start before the chunk start at it, a true token
+        uint32_t p = seg0 < kWarm ? 0u : seg0 - kWarm;
+        for (uint32_t q; (q = S.nxt4[p]) < seg0;) p = q;    // jumps stay short of the segment
+        for (uint32_t q; (q = S.nxt2[p]) < seg0;) p = q;
+        while (p < seg1) {
+            if (p >= seg0) vis |= 1u << (p - seg0);
+            p = next_of(nxt, p);
+            PROF_COUNT(15, 1);
+        }
+        x = p;
+    }
+    uint32_t es = vis ? seg0 + __builtin_ctz(vis) : x;
+    uint32_t nE = 0;
+    for (int it = 0; it <= kWave; ++it) {
+        // lane l - 1's values by DPP wave_shr:1 (a VALU operand, not an LDS permute)
+        const uint32_t pes = dpp<kWaveShr1>(0u, es), px = dpp<kWaveShr1>(0u, x);
+        nE = lane == 0 ? 0u : (pes >= seg0 ? pes : px);
+        bool valid = nE >= seg1 ? (vis == 0 && x == nE) : ((vis >> (nE - seg0)) & 1u) != 0;
+        uint64_t bad = __ballot(!valid);
+        PROF_COUNT(13, 1);
+        if (it == 0) PROF_COUNT(14, __popcll(bad));
+        if (bad == 0) break;
+        if (lane == __builtin_ctzll(bad)) {   // first inconsistent lane: re-walk from its true entry
+            vis = 0;
+            uint32_t p = nE;
+            while (p < seg1) {
+                vis |= 1u << (p - seg0);
+                p = next_of(nxt, p);
+            }
+            x = p;
+            es = vis ? seg0 + __builtin_ctz(vis) : x;
+        }
+    }
+    if (nE >= seg1) vis = 0;
+    else vis &= ~((1u << (nE - seg0)) - 1u);
+    tail = lane_of(x, kWave - 1);   // where the chain leaves the chunk
+    if (tail > (uint32_t)kLim && tail < kEnd) tail = kStop;   // (fast table: raw positions past the window)
+    const uint64_t has = __ballot(vis != 0);
+    const int last_lane = 63 - __builtin_clzll(has);
+    const uint32_t last_tok = lane_val(seg0 + 31 - __builtin_clz(vis | 1u), (uint32_t)last_lane);
+    return Parse{vis, tail, last_tok, last_lane, tail == kStop};
+}
+
+// ---------------------------------------------------------------- 4. sequence table
+// Sequence-major from a compact token list: every lane writes the positions of its
+// segment's tokens at base + j, then lane l of row i takes sequence k = 64 i + l, reads
+// its fields, gets its output start from a row scan plus the carry of the rows before,
+// and writes its entry once. Two rows per step, their byte reads issued together (three
+// LDS round trips per step). Errors in the reference's order: a 32-bit test per row pair,
+// and the exact 64-bit checks only from the first flagged pair on.
+// `rel`: an exported segment (relative output positions). `redo`: the table is not built --
+// a true token's match length field runs past one extension byte, which the fast next-token
+// table (fast_tab) took to be one: the chunk is parsed again with the exact table.
+struct SeqTable {
+    uint32_t nseq;        // sequences in S.t_seq (without the cut one)
+    int64_t total;        // their output bytes
+    uint32_t first_err;   // sequence << 3 | seq_error of the first failing one (0xFFFFFFFF: none)
+    bool redo;
+};
+template <bool XP>
+__device__ __forceinline__ SeqTable seq_table(const Ctx& c, DecShared& S, int lane, uint32_t rem, bool rel,
+                                              bool fast_tab, const Parse& P, Prof& prof) {
+    PROF(2);
+    const uint8_t* s = (const uint8_t*)S.stage;
+    const uint32_t seg0 = 16u * lane;
+    const uint32_t cnt = __popc(P.vis) - ((P.cut && lane == P.last_lane) ? 1u : 0u);
+    const uint32_t incl = wave_incl_scan(cnt, lane);
+    const uint32_t base = incl - cnt;
+    const uint32_t nseq = lane_of(incl, kWave - 1);
+    uint16_t* const tl = (uint16_t*)S.pms;   // (idle until the output phase; kMaxSeq * 2 bytes)
+    static_assert(sizeof(uint16_t) * (kMaxSeq + 2 * kWave) <= sizeof(S.pms), "token list fits in the pending starts");
+    {
+        uint32_t m = P.vis;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            tl[base + j] = (uint16_t)(seg0 + __builtin_ctz(m));
+            m &= m - 1;
+        }
+    }
+    __syncthreads();
+    // The 32-bit form of the five checks. With c.O <= c.cap (else every row is checked exactly),
+    // c.cap < 2^31, a table's output under 2^26 bytes (at most kMaxSeq sequences of under 2^17
+    // bytes each: both lengths are 16-bit fields of the entry) and offsets under 2^16, every sum
+    // below stays under 2^32, so the test is exact:
+    //   1  out + ll > cap                  <=>  X > capr, X = (out - c.O) + ll, capr = cap - c.O
+    //   2  ip + lit + ll > in_len          <=>  lit + ll > rem
+    //   3  off == 0, 4 off > out_off + out + ll + dict_len, 5 isolate and off > out + ll
+    //                                      <=>  off - 1 >= L45 + X (wrapping for off = 0), with
+    //      L45 = c.O + (isolate ? 0 : min(out_off + dict_len, 2^16)): past 2^16 check 4 cannot fail
+    // An exported segment (relative positions) has checks 2 and 3 only.
+    const bool exact_all = !rel && c.O > (int64_t)c.cap;
+    const uint32_t capr = rel || exact_all ? 0xFFFFFFFFu : (uint32_t)(c.cap - (int32_t)c.O);
+    const int64_t d4 = c.out_off + c.dict_len;
+    const uint32_t L45 = rel || exact_all ? 0x80000000u
+                                          : (uint32_t)c.O + (c.isolate ? 0u : (uint32_t)(d4 < 65536 ? d4 : 65536));
+    uint32_t carry = 0;   // output bytes of the rows before
+    uint32_t first_err = 0xFFFFFFFFu;
+    uint32_t flagged = 0xFFFFFFFFu;   // first rows the 32-bit test flags
+    constexpr int kRows = 2;
+    for (uint32_t i0 = 0; i0 < nseq; i0 += kRows * kWave) {
+        uint32_t p[kRows], tok[kRows], b1[kRows];
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            const uint32_t k = i0 + kWave * r + lane;
+            p[r] = k < nseq ? tl[k] : 0u;
+        }
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            tok[r] = s[p[r]];
+            b1[r] = s[p[r] + 1];
+        }
+        uint32_t q[kRows], lit[kRows], ll[kRows], o0[kRows], o1[kRows], mb[kRows];
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            const uint32_t x1 = (tok[r] >> 4) == 15 ? 1u : 0u;
+            ll[r] = x1 ? 15u + b1[r] : tok[r] >> 4;
+            lit[r] = p[r] + 1 + x1;
+            q[r] = lit[r] + ll[r];
+            // offset bytes inside the window (q + 2 <= kLim: a sequence may end on its last byte,
+            // as next_token accepts; s[q + 2] is still staged) -- past it only a long literal run
+            // (slow below)
+            const uint32_t qa = q[r] + 2 <= (uint32_t)kLim ? q[r] : 0u;
+            o0[r] = s[qa];
+            o1[r] = s[qa + 1];
+            mb[r] = s[qa + 2];
+        }
+        uint32_t off[kRows], ml[kRows];
+        bool rerun = false;   // a true token's match length runs on past one byte (fast table)
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            const bool live = i0 + kWave * r + lane < nseq;
+            off[r] = 0;
+            ml[r] = 0;
+            if (!live) {
+                ll[r] = 0;
+                continue;
+            }
+            uint32_t qj = q[r];
+            if ((tok[r] >> 4) == 15 && b1[r] == 255) {   // literal length field of 2+ bytes
+                uint32_t t = p[r] + 1, bb, llj = 15;
+                do { bb = s[t++]; llj += bb; } while (bb == 255);
+                ll[r] = llj;
+                lit[r] = t;
+                qj = t + llj;
+                if (qj < rem) { o0[r] = s[qj]; o1[r] = s[qj + 1]; mb[r] = s[qj + 2]; }
+            }
+            if (qj < rem) {
+                off[r] = o0[r] | (o1[r] << 8);
+                uint32_t m = tok[r] & 15;
+                if (m == 15) {
+                    if (mb[r] != 255) {
+                        m += mb[r];
+                    } else {
+                        rerun |= fast_tab;
+                        uint32_t t = qj + 2, bb;
+                        do { bb = s[t++]; m += bb; } while (bb == 255 && t < (uint32_t)kLim);
+                    }
+                }
+                ml[r] = m + 4;
+            }
+        }
+        if (__ballot(rerun)) return SeqTable{0u, 0, 0xFFFFFFFFu, true};
+        bool flag = false;
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            if (r > 0 && i0 + kWave * r >= nseq) break;
+            const uint32_t k = i0 + kWave * r + lane;
+            const uint32_t len = ll[r] + ml[r];
+            const uint32_t sc = wave_incl_scan(len, lane);
+            const uint32_t ro = carry + sc - len;   // output start, relative to c.O
+            carry += lane63(sc);
+            if (k < nseq) {
+                S.t_seq[k] = make_uint4((uint32_t)c.O + ro, lit[r] | (ll[r] << 16), off[r] | (ml[r] << 16), 0u);
+                const uint32_t X = ro + ll[r];
+                flag |= X > capr || lit[r] + ll[r] > rem || (ml[r] != 0 && off[r] - 1u >= L45 + X);
+            }
+        }
+        if (__ballot(flag) != 0 && flagged > i0) flagged = i0;
+    }
+    __syncthreads();
+    // the exact checks, from the first flagged rows on (absent on valid input); the first
+    // failing sequence ends them
+    for (uint32_t i0 = exact_all ? 0u : flagged; i0 < nseq && first_err == 0xFFFFFFFFu; i0 += kWave) {
+        const uint32_t k = i0 + lane;
+        uint32_t e = 0;
+        if (k < nseq) {
+            const SeqInfo q = seq_info(S, k);
+            e = seq_err<XP>(c, rel, c.O + (uint32_t)(q.out - (int32_t)c.O), (int64_t)c.ip + q.lit, q.ll, q.off, q.ml);
+        }
+        first_err = wave_min(e ? (k << 3) | e : 0xFFFFFFFFu);
+    }
+    return SeqTable{nseq, (int64_t)carry, first_err, false};
+}
+
+// ---------------------------------------------------------------- 5. cut sequence
+// The sequence the window could not hold (P.cut), parsed from memory: literals [clit, clit + cll),
+// match offset coff and length cml (0: none), the next token at cq (block-relative).
+// (Its parse is written out in decompress_block: as a function of its own it moved the export
+// kernel's register allocation and cost small text batches 1-6 %, profiles/refactor_phases.)
+struct CutSeq {
+    int64_t cq = 0, cll = 0, cml = 0, clit = 0;
+    uint32_t coff = 0;
+};
+
+// ---------------------------------------------------------------- advance
+// On to the next chunk: after the table (output up to tab_hi) and the cut sequence, if any.
+__device__ __forceinline__ void advance(Ctx& c, int64_t tab_hi, const Parse& P, const CutSeq& cs) {
+    c.O = tab_hi;
+    if (P.cut) {
+        c.O += cs.cll + cs.cml;
+        c.ip = (int32_t)(cs.cq < c.in_len ? cs.cq : c.in_len);
+    } else if (P.tail >= kEnd) {
+        c.ip = c.in_len;
+    } else {
+        c.ip += (int32_t)P.tail;
+    }
+}
+
+// ---------------------------------------------------------------- export (XP): a chunk
+// Export the chunk's sequences whose tokens lie in [seg_lo, seg_hi); the first one found is
+// the segment's entry, the first at or past seg_hi its exit. Then on to the next chunk (or,
+// a guess that met an impossible token before its segment, over again one byte past it).
+__device__ __forceinline__ void x_export_chunk(Ctx& c, const DecShared& S, XState& x, int lane, const Parse& P,
+                                               const SeqTable& T, const CutSeq& cs) {
+    const bool cut = P.cut;
+    const uint32_t nseq = T.nseq, seg_lo = x.seg_lo, seg_hi = x.seg_hi;
+    const int64_t tab_hi = c.O + T.total;
+    const uint32_t ipc = (uint32_t)c.ip;
+    const uint32_t ntot = nseq + (cut ? 1u : 0u);   // the cut sequence is number nseq
+    const uint32_t ecut = cut ? seq_err<true>(c, true, tab_hi, cs.clit, cs.cll, cs.coff, cs.cml) : 0u;
+    const uint32_t ferr = T.first_err != 0xFFFFFFFFu ? T.first_err : (ecut ? ((nseq << 3) | ecut) : 0xFFFFFFFFu);
+    const uint32_t fk = ferr == 0xFFFFFFFFu ? ntot : (ferr >> 3);
+    auto x_tok = [&](uint32_t k) -> uint32_t {   // token position (block-relative)
+        if (k >= nseq) return ipc + P.last_tok;
+        const SeqInfo q = seq_info(S, k);
+        return ipc + (uint32_t)q.lit - 1u - (q.ll >= 15 ? (uint32_t)(q.ll - 15) / 255u + 1u : 0u);
+    };
+    auto x_out = [&](uint32_t k) -> int64_t { return k >= nseq ? tab_hi : (int64_t)S.t_seq[k].x; };
+    uint32_t k0 = ntot, k1 = ntot;
+    for (uint32_t r = 0; 64u * r < ntot; ++r) {
+        const uint32_t k = 64u * r + lane;
+        const uint32_t t = k < ntot ? x_tok(k) : 0xFFFFFFFFu;
+        const uint64_t m0 = __ballot(k < ntot && t >= seg_lo), m1 = __ballot(k < ntot && t >= seg_hi);
+        if (k0 == ntot && m0) k0 = 64u * r + (uint32_t)__builtin_ctzll(m0);
+        if (k1 == ntot && m1) k1 = 64u * r + (uint32_t)__builtin_ctzll(m1);
+    }
+    bool restart = false;
+    if (!x.started && fk < k0) {
+        // an error before the segment: a wrong walk, or an earlier segment's error (which
+        // that segment's parse reports) -- never this segment's. A guess starts over one
+        // byte past the impossible token (text: an offset of 0 read from the wrong bytes
+        // failed 22 of a 4 MiB block's 255 guesses, which then waited for re-parses)
+        if (x.pass == 0 && x.restart < kSegRestarts) {
+            restart = true;
+            ++x.restart;
+        } else {
+            x.fail = x.done = true;
+        }
+    } else {
+        if (!x.started && k0 < ntot) {
+            x.started = true;
+            x.G = x_tok(k0);
+            x.OG = x_out(k0);
+        }
+        if (x.started) {
+            const uint32_t ke = fk < k1 ? fk + 1 : k1;   // with the failing one (checks 1, 4, 5)
+            for (uint32_t k = k0 + lane; k < ke; k += kWave) {
+                uint4 e;
+                if (k < nseq) {
+                    const SeqInfo q = seq_info(S, k);
+                    e = make_uint4((uint32_t)(x_out(k) - x.OG), ipc + (uint32_t)q.lit, (uint32_t)q.ll,
+                                   q.ml ? (uint32_t)q.off : 0u);
+                } else {
+                    e = make_uint4((uint32_t)(tab_hi - x.OG), (uint32_t)cs.clit, (uint32_t)cs.cll,
+                                   cs.cml ? cs.coff : 0u);
+                }
+                x.xs[x.nx + (k - k0)] = e;
+            }
+            if (fk < k1) {
+                x.err = ((x.nx + (fk - k0)) << 3) | (ferr & 7u);
+                x.done = true;
+            } else if (k1 < ntot) {
+                x.done = true;
+                x.X = x_tok(k1);
+                x.olen = (uint32_t)(x_out(k1) - x.OG);
+            }
+            x.nx += ke - k0;
+        }
+    }
+    if (restart) {
+        c.ip = (int32_t)(x_tok(fk) + 1u);
+        c.O = 0;
+    } else if (!x.done) {
+        advance(c, tab_hi, P, cs);
+        if ((uint32_t)c.ip >= seg_hi && c.ip < c.in_len) {   // the chain leaps the segment's end
+            if (!x.started) {
+                x.started = true;
+                x.G = (uint32_t)c.ip;
+                x.OG = c.O;
+            }
+            x.done = true;
+            x.X = (uint32_t)c.ip;
+            x.olen = (uint32_t)(c.O - x.OG);
+        }
+    }
+    __syncthreads();
+}
+
+// The segment's record, once its exit is found or the block ends.
+__device__ __forceinline__ void x_finish(const DecArgs& a, const Ctx& c, XState& x, int lane, uint32_t sg) {
+    if (!x.done) {   // the block's end
+        if (!x.started) {
+            x.G = (uint32_t)c.in_len;
+            x.OG = c.O;
+        }
+        x.X = (uint32_t)c.in_len;
+        x.olen = (uint32_t)(c.O - x.OG);
+    }
+    if (lane == 0) {
+        SegRec* const xr = x.xr;
+        xr->entry = x.G;
+        xr->exit = x.X;
+        xr->cnt = x.nx;
+        xr->olen = x.olen;
+        xr->err = x.err;
+        xr->fail = (x.fail || (a.xforce && sg > 0 && (a.xforce == 2 ? x.pass != 1 : x.pass == 0))) ? 1u : 0u;
+        if (x.pass == 1)   // the exact re-parse of phase 1: final
+            __hip_atomic_store(&xr->fin, (x.err != 0xFFFFFFFFu ? kFinErr : x.X) + 1u, __ATOMIC_RELEASE,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---------------------------------------------------------------- 6. output rounds
+// Output -> sequence map for remap_src, in the (now idle) next-token table; returns its shift.
+__device__ __forceinline__ uint32_t source_map(const Ctx& c, DecShared& S, int lane, uint32_t nseq, int64_t total) {
+    // output -> sequence map granule: 32 bytes for long sequences (tiles216: 16 B costs 1.8 %),
+    // 16 for short ones (text: 32 B costs 6 %, more sequences per granule to step over)
+    uint32_t msh = total >= 32u * nseq ? 5u : 4u;
+    while ((total >> msh) >= kLim) ++msh;
+    for (uint32_t k = lane; k < nseq; k += kWave) {
+        const uint32_t t0 = S.t_seq[k].x - (uint32_t)c.O;
+        const uint32_t t1 = (k + 1 < nseq ? S.t_seq[k + 1].x : (uint32_t)(c.O + total)) - (uint32_t)c.O;
+        for (uint32_t b = (t0 + (1u << msh) - 1) >> msh; (b << msh) < t1; ++b) S.nxt[b] = (uint16_t)k;
+    }
+    __syncthreads();
+    return msh;
+}
+
+// Round 1: all literal runs (from LDS) and every match whose source lies, or maps back to,
+// output finished by earlier chunks. Returns the pending matches: bit i = that of
+// sequence 64 i + lane.
+__device__ __forceinline__ uint32_t round1(const Ctx& c, DecShared& S, int lane, uint32_t nseq, uint32_t msh, Prof& prof) {
+    uint32_t pend = 0;    // bit i: the match of sequence 64i+lane is still to be written
+    uint32_t ready = 0;   // bit i: ... is written by this lane in this round
+    uint32_t rbits = 0;   // bit i: ... reads a remapped source (SeqInfo::rsrc)
+    uint32_t nlit_pack = 0;   // byte i (rows < 4): literal prefix of a split match (remap_src 3)
+    for (uint32_t i = 0; 64 * i < nseq; ++i) {            // round 1
+        const uint32_t k = 64 * i + lane;
+        Run M = no_run(), ML = no_run();
+        SeqInfo q = seq_info(S, k < nseq ? k : 0u);
+        if (k >= nseq) q.ll = 0;
+        {   // the literal runs first (their registers are free before the remap)
+            const Run L = q.ll ? Run{q.out, q.ll, q.lit, 0, R_LDS} : no_run();
+            const bool longL = L.n > kLaneBytes;
+            lane_literals(c, S, longL ? no_run() : L);
+            for (uint64_t lm = __ballot(longL); lm; lm &= lm - 1) wave_run(c, S, lane, shfl_run(L, __builtin_ctzll(lm)), no_pat());
+        }
+        PROF(23);
+        if (k < nseq) {
+            const int32_t t0 = q.out;
+            M = match_run(c, t0 + q.ll, q.off, q.ml);
+            if (M.n == 0) {
+                M.kind = R_NONE;
+            } else if (match_src_end(M) > (int32_t)c.O) {
+                // the source is output of this table: map it back through the
+                // sequences that wrote it, else wait for a later round
+                int32_t rs = M.src, re = match_src_end(M), li = 0, nl = 0;
+                const int r = (M.kind == R_HIST && M.period == 0)
+                                  ? remap_src(c, S, nseq, msh, rs, re, li, nl, i < 4)
+                                  : 0;
+                if (r == 3) {   // literal prefix from the stage, the rest from finished output
+                    ML = Run{M.y, nl, li, 0, R_LDS};
+                    M.y += nl;
+                    M.n -= nl;
+                    nlit_pack |= (uint32_t)nl << (8 * i);
+                }
+                if (r == 1 || r == 3) {
+                    M.src = rs;
+                    if (c.out_off + rs < 16) M.kind = R_BYTES;
+                    S.t_seq[k].w = (uint32_t)(rs + (r == 3 ? kSplitBase : kMemoBase));
+                    rbits |= 1u << i;
+                } else if (r == 2) {
+                    ML = Run{M.y, M.n, li, 0, R_LDS};
+                    M.kind = R_NONE;
+                } else {
+                    pend |= 1u << i;
+                    M.kind = R_NONE;
+                }
+            }
+        }
+        const bool longM = M.kind != R_NONE && M.n > kLaneBytes;
+        const bool longML = ML.n > kLaneBytes;
+        const bool fastM = M.kind == R_HIST && M.period == 0 && M.n >= 16;
+        if (M.kind != R_NONE && !longM && fastM) ready |= 1u << i;
+        PROF(16);
+        lane_literals(c, S, longML ? no_run() : ML);
+        PROF(17);
+        for (uint64_t lm = __ballot(longML); lm; lm &= lm - 1) wave_run(c, S, lane, shfl_run(ML, __builtin_ctzll(lm)), no_pat());
+        if (M.kind != R_NONE && !longM && !fastM) lane_slow_run(c, S, M);
+        for (uint64_t mm = __ballot(longM); mm; mm &= mm - 1) wave_run(c, S, lane, shfl_run(M, __builtin_ctzll(mm)), pat_round1(S));
+        PROF(18);
+    }
+    piece_pipe(c, S, ready, rbits, lane, nseq, nlit_pack);
+    return pend;
+}
+
+// Rounds 2, 3, ...: after the previous round's stores are complete, every pending match
+// whose source range meets no pending match.
+__device__ __forceinline__ void later_rounds(const Ctx& c, DecShared& S, int lane, uint32_t nseq, uint32_t pend,
+                                             Prof& prof) {
+    for (; LZ4MI_ABLATE != 6;) {
+        uint32_t np = 0;
+        for (uint32_t i = 0; 64 * i < nseq; ++i) {
+            const bool pk = (pend >> i) & 1u;
+            const uint64_t bal = __ballot(pk);
+            if (pk) {
+                const uint32_t k = 64 * i + lane;
+                const uint32_t idx = np + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
+                                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                const SeqInfo q = seq_info(S, k);
+                const int32_t ms = q.out + q.ll;
+                S.pms[idx] = (uint32_t)ms;
+                S.pme[idx] = (uint32_t)(ms + q.ml > c.cap ? c.cap : ms + q.ml);
+            }
+            np += (uint32_t)__popcll(bal);
+        }
+        if (np == 0) break;
+        PROF_COUNT(11, 1);
+        __syncthreads();
+        wait_vmem();      // the previous round's stores are complete
+        PROF(20);
+        uint32_t ready = 0;   // bit i: the match of sequence 64i+lane is written by this lane in this round
+        for (uint32_t i = 0; 64 * i < nseq; ++i) {
+            if (__ballot((pend >> i) & 1u) == 0) continue;
+            Run M = no_run();
+            if ((pend >> i) & 1u) {
+                const uint32_t k = 64 * i + lane;
+                const SeqInfo q = seq_info(S, k);
+                M = match_run(c, q.out + q.ll, q.off, q.ml);
+                // first pending match ending past the source start: ready if it starts at or past the source end
+                const int32_t rs = M.src, re = match_src_end(M);
+                uint32_t lo = 0, hi = np;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if ((int32_t)S.pme[mid] > rs) hi = mid;
+                    else lo = mid + 1;
+                }
+                if (lo >= np || (int32_t)S.pms[lo] >= re) pend &= ~(1u << i);
+                else M.kind = R_NONE;
+            }
+            const bool longM = M.kind != R_NONE && M.n > kLaneBytes;
+            const bool fastM = M.kind == R_HIST && M.period == 0 && M.n >= 16;
+            if (M.kind != R_NONE && !longM && fastM) ready |= 1u << i;
+            if (M.kind != R_NONE && !longM && !fastM) lane_slow_run(c, S, M);
+            for (uint64_t mm = __ballot(longM); mm; mm &= mm - 1) wave_run(c, S, lane, shfl_run(M, __builtin_ctzll(mm)), pat_rounds(S));
+        }
+        piece_pipe(c, S, ready, 0u, lane, nseq, 0u);
+        __syncthreads();
+    }
+}
+
+// The table's sequences, written (T.total bytes from c.O).
+__device__ __forceinline__ void output_rounds(const Ctx& c, DecShared& S, int lane, const SeqTable& T, Prof& prof) {
+    const uint32_t msh = source_map(c, S, lane, T.nseq, T.total);
+    PROF(22);
+    const uint32_t pend = round1(c, S, lane, T.nseq, msh, prof);
+    PROF(19);
+    later_rounds(c, S, lane, T.nseq, pend, prof);
+}
+
+// ---------------------------------------------------------------- 7. F1 replay (reference mode)
+// Both return the block's status: 0, or -9 where a rewrite reads below the block's start.
+// The table's sequences, after their output.
+__device__ __forceinline__ int32_t f1_table(const Ctx& c, const DecShared& S, int lane, uint32_t nseq) {
+    // candidates first, from the sequence table alone (offset >= 8, length < 8): a chunk
+    // without one -- every tiles216 chunk -- neither drains its stores here nor reads
+    // them back, so they keep draining beside the next chunk's parse as in spec mode
+    bool cand = false;
+    for (uint32_t k = lane; k < nseq; k += kWave) {
+        const SeqInfo q = seq_info(S, k);
+        cand |= q.ml != 0 && q.ml < 8 && q.off >= 8;
+    }
+    if (__ballot(cand)) {
+        wait_vmem();    // this chunk's stores are complete before they are read back
+        uint32_t dv = 0;
+        for (uint32_t k = lane; k < nseq; k += kWave) {
+            const SeqInfo q = seq_info(S, k);
+            dv |= f1_changes(c, q.out + q.ll, q.off, q.ml);
+        }
+        if (__ballot(dv & 2u)) return -9;
+        if (__ballot(dv)) f1_fixup(c, S, lane, nseq, false, 0, 0, 0);
+    }
+    return 0;
+}
+
+// The cut sequence's match (starting at ms), after the table's F1 replay (it reads the replayed
+// bytes, as the reference's copy does); the tables are idle now: all of LDS can hold a
+// periodic pattern. Then (f1check) its own tail rewrite, after its copy as in the reference.
+__device__ __forceinline__ int32_t cut_match(const Ctx& c, DecShared& S, int lane, int32_t ms, const CutSeq& cs,
+                                             bool f1check) {
+    const Run M = match_run(c, ms, (int32_t)cs.coff, (int32_t)cs.cml);
+    if (M.n > 0) {
+        wait_vmem();    // everything below the match is read back as history
+        wave_run(c, S, lane, M, pat_all(S));
+    }
+    if (f1check && cs.cml != 0 && cs.cml < 8 && cs.coff >= 8) {
+        wait_vmem();
+        const uint32_t dv = lane == 0 ? f1_changes(c, ms, (int32_t)cs.coff, (int32_t)cs.cml) : 0u;
+        if (__ballot(dv & 2u)) return -9;
+        if (__ballot(dv)) f1_fixup(c, S, lane, 0, true, (int64_t)ms, (int32_t)cs.coff, (int32_t)cs.cml);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- the block's loop
+constexpr bool kOutput = LZ4MI_ABLATE == 0 || LZ4MI_ABLATE >= 4;      // (else timing only: nothing is written)
+constexpr bool kParseOnly = LZ4MI_ABLATE == 2 || LZ4MI_ABLATE == 3;   // (timing only: steps 1-3)
+
+// XP: the small-batch export, a wave per segment of the block (x_enter); LK: a linked window.
+template <bool XP, bool LK = false>
+__device__ __forceinline__ void decompress_block(const DecArgs& a) {
+    __shared__ DecShared S;
+    const int lane = threadIdx.x;
+    const uint32_t nseg = XP ? a.xsegs : 1u;   // XP: waves per block (one per segment)
+    if (blockIdx.x >= a.nblocks * nseg) return;
+    const uint32_t wblk = XP ? blockIdx.x / nseg : blockIdx.x;   // (XP: block-major, segments of a block on
+    const uint32_t sg = XP ? blockIdx.x - wblk * nseg : 0u;       //  consecutive CUs, every XCD)
+    if (LK && uniform(a.xcnt[wblk]) == kNotExported) return;     // stored, refused or after a failure: not parsed
+    const uint32_t b = a.order ? uniform(a.order[wblk]) : wblk;
+    if (!XP && a.redo && !uniform(a.redo[b])) return;   // (small batches, reference mode: the blocks to redo)
+#if LZ4MI_TIMELINE
+    const uint64_t tl_t0 = wall_clock64();
+#endif
+    // the block's scalars in SGPRs (readfirstlane): as VGPRs the compiler would keep
+    // per-lane copies of values derived from them and spill those to scratch
+    const uint64_t in_off = uniform64(a.in_off[b]), out_off = uniform64(a.out_off[b]);
+    const uint32_t out_cap = uniform(a.out_cap[b]);
+    Ctx c;
+    c.blk = a.in + in_off;
+    const uint32_t word = uniform(a.in_len[b]);
+    c.in_len = (int32_t)(a.frame_words ? word & 0x7FFFFFFFu : word);
+    c.out_off = (int64_t)out_off;
+    c.dst = a.out + out_off;
+    c.cap = out_cap > 0x7FFFFFFFu ? 0x7FFFFFFF : (int32_t)out_cap;
+    c.dict = a.dict;
+    c.dict_len = a.dict ? (int32_t)a.dict_len : 0;
+    c.isolate = a.isolate;
+    c.ip = 0;
+    c.O = 0;
+    if (a.frame_words && (word & 0x80000000u)) {
+        stored_block(a, c, b, out_cap, lane);
+        return;
+    }
+    XState x;   // (XP)
+    if constexpr (XP) {
+        if (!x_enter<LK>(a, c, x, lane, wblk, sg, nseg, out_cap)) return;
+    }
+    const bool xp = XP && x.on;   // parsed for export; else decoded here
 #if LZ4MI_LL_ADAPT
     const bool lat_bound = (uint64_t)c.in_len * 2 < (uint64_t)out_cap;   // ratio > 2: a chain of short copies
     unsigned int* lat = &g_lat_active[32 * xcc_id()];
     if (lat_bound && lane == 0) atomicAdd(lat, 1u);
 #endif
-    uint4 pf0 = make_uint4(0, 0, 0, 0), pf1 = pf0;   // the next chunk's staged bytes, loaded early
-    bool have_pf = false;
-    int64_t pf_at = -1;                    // compressed position pf0/pf1 were loaded from
+    Prefetch pf;
+    Prof prof;
 #if LZ4MI_PROFILE
-    uint64_t prof[24] = {0};
-    uint64_t prof_t = wall_clock64();
+    prof = Prof{{0}, (uint64_t)wall_clock64()};
 #endif
-
-    if (XP && xp) {
-        c.O = 0;
-        have_pf = false;
-        c.ip = x_pass ? (int32_t)x_entry
-                      : (seg_lo >= (uint32_t)c.in_len ? c.in_len : (int32_t)(seg_lo - min(seg_lo, kSegWarm)));
-        x_started = x_done = x_fail = false;
-        x_G = x_X = nx = x_olen = 0;
-        x_err = 0xFFFFFFFFu;
-        x_OG = 0;
-    }
+    int32_t status = 0;
     while (c.ip < c.in_len) {
-        if (XP && x_done) break;   // (XP: the segment's exit found)
+        if (XP && x.done) break;   // (XP: the segment's exit found)
         PROF_COUNT(10, 1);
-        // ---- 1. stage [ip, ip + kLim) (16-byte unaligned loads, issued during
-        // the previous chunk's output phase, ahead of its stores) -------------
-        // (each branch writes the stage itself: a write after the join would wait for the
-        // fresh loads of the first branch on both, i.e. for every store still in flight)
-        if (!have_pf || pf_at != c.ip) {
-            const uint4 a = stage_piece(c, (int64_t)c.ip + 16 * opaque(lane));
-            uint4 b = make_uint4(0, 0, 0, 0);
-            if (lane < kStageWords / 4 - kWave) b = stage_piece(c, (int64_t)c.ip + 16 * (kWave + opaque(lane)));
-            __builtin_memcpy((uint8_t*)S.stage + 16 * lane, &a, 16);
-            if (lane < kStageWords / 4 - kWave) __builtin_memcpy((uint8_t*)S.stage + 16 * (kWave + lane), &b, 16);
-        } else {
-            __builtin_memcpy((uint8_t*)S.stage + 16 * lane, &pf0, 16);
-            if (lane < kStageWords / 4 - kWave) __builtin_memcpy((uint8_t*)S.stage + 16 * (kWave + lane), &pf1, 16);
-        }
-        have_pf = false;
-        __syncthreads();
-        const uint8_t* s = (const uint8_t*)S.stage;
+        stage_chunk(c, S, pf, lane);                                        // 1
         const uint32_t rem = (uint32_t)(c.in_len - c.ip);
-
-        const uint32_t seg0 = 16u * lane, seg1 = seg0 + 16;
-        uint32_t vis, tail;
-        bool fast_tab = rem > kFastRem;
-    parse:
-        {
-        PROF(0);
-        // Wave priorities by phase (the 4 waves of a SIMD are in different phases):
-        // output rounds 3 > walks 1 > next-token table 0. The copies' loads and
-        // stores go out first and the LDS-bound parse fills the gaps: tiles216 -0.9 %,
-        // mix -2.5 %, copy -1.5 % (A/B in one process, profiles/r02j/prio_ab.json).
-        __builtin_amdgcn_s_setprio(0);
-        // ---- 2. next-token table -----------------------------------------
-        // Away from the block's end (fast_tab) four positions per lane from two stage
-        // dwords, assuming length fields of at most one extension byte: a token whose
-        // literal field runs on (b1 == 255) stops the chain (the cut path parses it), and
-        // a match field that runs on (checked on the true tokens in the table build) sends
-        // the chunk back here for the exact table. Near the end: the exact table.
-        uint16_t* nxt = S.nxt;
-        if (fast_tab) {
-            next_table_fast(S.stage, nxt, lane);
-        } else {   // all positions' fields read at once; the rare longer length fields afterwards
-            static_assert(kChunk % kWave == 0, "whole rows per lane");
-            uint32_t slm = 0;
-#pragma unroll
-            for (int i = 0; i < kChunk / kWave; ++i) {
-                bool slow;
-                const uint32_t v = next_fast(s, lane + kWave * i, rem, slow);
-                slm |= (slow ? 1u : 0u) << i;
-                nxt[lane + kWave * i] = enc_next(v);
-            }
-            if (__ballot(slm != 0)) {
-                for (uint32_t m = slm; m; m &= m - 1) {
-                    const uint32_t p = lane + kWave * __builtin_ctz(m);
-                    nxt[p] = enc_next(next_token(s, p, rem));
-                }
-            }
-        }
-        __syncthreads();
-        // 2- and 4-step jumps (the warm-up walks only need where the chain lands)
-        jump_table(nxt, S.nxt2, lane);
-        __syncthreads();
-        jump_table(S.nxt2, S.nxt4, lane);
-        __syncthreads();
-#if LZ4MI_ABLATE == 3
-        c.ip += kChunk;
-        __syncthreads();
-        continue;
-#endif
-
-        PROF(1);
-        __builtin_amdgcn_s_setprio(1);
-        // ---- 3. speculative walks + certification -------------------------
-        uint32_t x;
-        vis = 0;
-        {   // warm-up walk; lanes whose warm-up would start before the chunk start at it, a true token
-            uint32_t p = seg0 < kWarm ? 0u : seg0 - kWarm;
-            for (uint32_t q; (q = S.nxt4[p]) < seg0;) p = q;    // jumps stay short of the segment
-            for (uint32_t q; (q = S.nxt2[p]) < seg0;) p = q;
-            while (p < seg1) {
-                if (p >= seg0) vis |= 1u << (p - seg0);
-                p = next_of(nxt, p);
-                PROF_COUNT(15, 1);
-            }
-            x = p;
-        }
-        uint32_t es = vis ? seg0 + __builtin_ctz(vis) : x;
-        uint32_t nE = 0;
-        for (int it = 0; it <= kWave; ++it) {
-            // lane l - 1's values by DPP wave_shr:1 (a VALU operand, not an LDS permute)
-            const uint32_t pes = dpp<kWaveShr1>(0u, es), px = dpp<kWaveShr1>(0u, x);
-            nE = lane == 0 ? 0u : (pes >= seg0 ? pes : px);
-            bool valid = nE >= seg1 ? (vis == 0 && x == nE) : ((vis >> (nE - seg0)) & 1u) != 0;
-            uint64_t bad = __ballot(!valid);
-            PROF_COUNT(13, 1);
-            if (it == 0) PROF_COUNT(14, __popcll(bad));
-            if (bad == 0) break;
-            if (lane == __builtin_ctzll(bad)) {   // first inconsistent lane: re-walk from its true entry
-                vis = 0;
-                uint32_t p = nE;
-                while (p < seg1) {
-                    vis |= 1u << (p - seg0);
-                    p = next_of(nxt, p);
-                }
-                x = p;
-                es = vis ? seg0 + __builtin_ctz(vis) : x;
-            }
-        }
-        if (nE >= seg1) vis = 0;
-        else vis &= ~((1u << (nE - seg0)) - 1u);
-        tail = lane_of(x, kWave - 1);   // where the chain leaves the chunk
-        if (tail > (uint32_t)kLim && tail < kEnd) tail = kStop;   // (fast table: raw positions past the window)
-        }
-        (void)seg1;
-        const uint64_t has = __ballot(vis != 0);
-        const int last_lane = 63 - __builtin_clzll(has);
-        const uint32_t last_tok = lane_val(seg0 + 31 - __builtin_clz(vis | 1u), (uint32_t)last_lane);
-        const bool cut = tail == kStop;
-        if (!cut && tail < kEnd && (int64_t)c.ip + tail < c.in_len) {
+        // away from the block's end the fast next-token table; where it does not hold
+        // (T.redo) the chunk once more, with the exact one
+        Parse P;
+        SeqTable T;
+        for (bool fast_tab = rem > kFastRem;; fast_tab = false) {
+            P = parse_chunk(S, lane, rem, fast_tab, prof);                  // 2, 3
             // the next chunk's bytes: loaded while this chunk's table is built
-            int64_t nip = (int64_t)c.ip + tail;
-            pf0 = stage_piece(c, nip + 16 * opaque(lane));
-            if (lane < kStageWords / 4 - kWave) pf1 = stage_piece(c, nip + 16 * (kWave + opaque(lane)));
-            pf_at = nip;
-            have_pf = true;
+            if (LZ4MI_ABLATE != 3 && !P.cut && P.tail < kEnd && (int64_t)c.ip + P.tail < c.in_len)
+                prefetch(c, pf, (int64_t)c.ip + P.tail, lane);
+            if (kParseOnly) break;
+            T = seq_table<XP>(c, S, lane, rem, xp, fast_tab, P, prof);      // 4
+            if (!T.redo) break;
+            wait_vmem();          // (no load in flight into the parse: its registers are free)
+            settle(pf);
+            __syncthreads();
         }
-#if LZ4MI_ABLATE == 2
-        c.ip = tail == kEnd ? c.in_len : c.ip + (cut ? kChunk : (int32_t)tail);
-        __syncthreads();
-        continue;
-#endif
-
-        PROF(2);
-        // ---- 4. sequence table -----------------------------------------
-        // Sequence-major from a compact token list: every lane writes the positions of its
-        // segment's tokens at base + j, then lane l of row i takes sequence k = 64 i + l, reads
-        // its fields, gets its output start from a row scan plus the carry of the rows before,
-        // and writes its entry once. Two rows per step, their byte reads issued together (three
-        // LDS round trips per step). Errors in the reference's order: a 32-bit test per row pair,
-        // and the exact 64-bit checks only from the first flagged pair on.
-        const uint32_t cnt = __popc(vis) - ((cut && lane == last_lane) ? 1u : 0u);
-        const uint32_t incl = wave_incl_scan(cnt, lane);
-        const uint32_t base = incl - cnt;
-        const uint32_t nseq = lane_of(incl, kWave - 1);
-        uint16_t* const tl = (uint16_t*)S.pms;   // (idle until the output phase; kMaxSeq * 2 bytes)
-        static_assert(sizeof(uint16_t) * (kMaxSeq + 2 * kWave) <= sizeof(S.pms), "token list fits in the pending starts");
-        {
-            uint32_t m = vis;
-            for (uint32_t j = 0; j < cnt; ++j) {
-                tl[base + j] = (uint16_t)(seg0 + __builtin_ctz(m));
-                m &= m - 1;
-            }
-        }
-        __syncthreads();
-        // The 32-bit form of the five checks. With c.O <= c.cap (else every row is checked exactly),
-        // c.cap < 2^31, a table's output under 2^26 bytes (at most kMaxSeq sequences of under 2^17
-        // bytes each: both lengths are 16-bit fields of the entry) and offsets under 2^16, every sum
-        // below stays under 2^32, so the test is exact:
-        //   1  out + ll > cap                  <=>  X > capr, X = (out - c.O) + ll, capr = cap - c.O
-        //   2  ip + lit + ll > in_len          <=>  lit + ll > rem
-        //   3  off == 0, 4 off > out_off + out + ll + dict_len, 5 isolate and off > out + ll
-        //                                      <=>  off - 1 >= L45 + X (wrapping for off = 0), with
-        //      L45 = c.O + (isolate ? 0 : min(out_off + dict_len, 2^16)): past 2^16 check 4 cannot fail
-        // An exported segment (relative positions) has checks 2 and 3 only.
-        const bool rel = XP && xp;
-        const bool exact_all = !rel && c.O > (int64_t)c.cap;
-        const uint32_t capr = rel || exact_all ? 0xFFFFFFFFu : (uint32_t)(c.cap - (int32_t)c.O);
-        const int64_t d4 = c.out_off + c.dict_len;
-        const uint32_t L45 = rel || exact_all ? 0x80000000u
-                                              : (uint32_t)c.O + (c.isolate ? 0u : (uint32_t)(d4 < 65536 ? d4 : 65536));
-        uint32_t carry = 0;   // output bytes of the rows before
-        uint32_t first_err = 0xFFFFFFFFu;
-        uint32_t flagged = 0xFFFFFFFFu;   // first rows the 32-bit test flags
-        constexpr int kRows = 2;
-        for (uint32_t i0 = 0; i0 < nseq; i0 += kRows * kWave) {
-            uint32_t p[kRows], tok[kRows], b1[kRows];
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) {
-                const uint32_t k = i0 + kWave * r + lane;
-                p[r] = k < nseq ? tl[k] : 0u;
-            }
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) {
-                tok[r] = s[p[r]];
-                b1[r] = s[p[r] + 1];
-            }
-            uint32_t q[kRows], lit[kRows], ll[kRows], o0[kRows], o1[kRows], mb[kRows];
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) {
-                const uint32_t x1 = (tok[r] >> 4) == 15 ? 1u : 0u;
-                ll[r] = x1 ? 15u + b1[r] : tok[r] >> 4;
-                lit[r] = p[r] + 1 + x1;
-                q[r] = lit[r] + ll[r];
-                // offset bytes inside the window (q + 2 <= kLim: a sequence may end on its last byte,
-                // as next_token accepts; s[q + 2] is still staged) -- past it only a long literal run
-                // (slow below)
-                const uint32_t qa = q[r] + 2 <= (uint32_t)kLim ? q[r] : 0u;
-                o0[r] = s[qa];
-                o1[r] = s[qa + 1];
-                mb[r] = s[qa + 2];
-            }
-            uint32_t off[kRows], ml[kRows];
-            bool rerun = false;   // a true token's match length runs on past one byte (fast table)
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) {
-                const bool live = i0 + kWave * r + lane < nseq;
-                off[r] = 0;
-                ml[r] = 0;
-                if (!live) {
-                    ll[r] = 0;
-                    continue;
-                }
-                uint32_t qj = q[r];
-                if ((tok[r] >> 4) == 15 && b1[r] == 255) {   // literal length field of 2+ bytes
-                    uint32_t t = p[r] + 1, bb, llj = 15;
-                    do { bb = s[t++]; llj += bb; } while (bb == 255);
-                    ll[r] = llj;
-                    lit[r] = t;
-                    qj = t + llj;
-                    if (qj < rem) { o0[r] = s[qj]; o1[r] = s[qj + 1]; mb[r] = s[qj + 2]; }
-                }
-                if (qj < rem) {
-                    off[r] = o0[r] | (o1[r] << 8);
-                    uint32_t m = tok[r] & 15;
-                    if (m == 15) {
-                        if (mb[r] != 255) {
-                            m += mb[r];
-                        } else {
-                            rerun |= fast_tab;
-                            uint32_t t = qj + 2, bb;
-                            do { bb = s[t++]; m += bb; } while (bb == 255 && t < (uint32_t)kLim);
-                        }
-                    }
-                    ml[r] = m + 4;
-                }
-            }
-            if (__ballot(rerun)) {   // the fast table assumed a one-byte match length field
-                fast_tab = false;
-                wait_vmem();          // (no load in flight into the parse: its registers are free)
-                settle(pf0);
-                settle(pf1);
-                __syncthreads();
-                goto parse;
-            }
-            bool flag = false;
-#pragma unroll
-            for (int r = 0; r < kRows; ++r) {
-                if (r > 0 && i0 + kWave * r >= nseq) break;
-                const uint32_t k = i0 + kWave * r + lane;
-                const uint32_t len = ll[r] + ml[r];
-                const uint32_t sc = wave_incl_scan(len, lane);
-                const uint32_t ro = carry + sc - len;   // output start, relative to c.O
-                carry += lane63(sc);
-                if (k < nseq) {
-                    S.t_seq[k] = make_uint4((uint32_t)c.O + ro, lit[r] | (ll[r] << 16), off[r] | (ml[r] << 16), 0u);
-                    const uint32_t X = ro + ll[r];
-                    flag |= X > capr || lit[r] + ll[r] > rem || (ml[r] != 0 && off[r] - 1u >= L45 + X);
-                }
-            }
-            if (__ballot(flag) != 0 && flagged > i0) flagged = i0;
-        }
-        __syncthreads();
-        // the exact checks, from the first flagged rows on (absent on valid input); the first
-        // failing sequence ends them
-        for (uint32_t i0 = exact_all ? 0u : flagged; i0 < nseq && first_err == 0xFFFFFFFFu; i0 += kWave) {
-            const uint32_t k = i0 + lane;
-            uint32_t e = 0;
-            if (k < nseq) {
-                const SeqInfo q = seq_info(S, k);
-                e = seq_err<XP>(c, xp, c.O + (uint32_t)(q.out - (int32_t)c.O), (int64_t)c.ip + q.lit, q.ll, q.off, q.ml);
-            }
-            first_err = wave_min(e ? (k << 3) | e : 0xFFFFFFFFu);
-        }
-        const int64_t total = carry;
-        if (first_err != 0xFFFFFFFFu && !(XP && xp)) { status = err_status(first_err & 7); break; }
-
-        PROF(3);
-        // ---- 6. the sequence the window could not hold: parse it from memory
-        int64_t cq = 0, cll = 0, cml = 0, clit = 0;
-        uint32_t coff = 0;
-        if (cut) {
-            // token and literal length from the staged bytes while they last
-            constexpr uint32_t kStaged = 16 * (kStageWords / 4);
-            uint32_t r = last_tok;
-            const uint32_t tok = s[r++];
-            cll = tok >> 4;
-            bool more = cll == 15;
-            while (more && r < kStaged) {
-                const uint32_t b = s[r++];
-                cll += b;
-                more = b == 255;
-            }
-            int64_t q = (int64_t)c.ip + r;
-            if (more) cll += wave_varint(c, lane, q);
-            clit = q;
-            q += cll;
-            if (q < c.in_len) {
-                // offset and match length: one 16-byte load covers them unless the length runs on
-                uint32_t w[4];
-                if (q + 16 <= c.in_len) {
-                    __builtin_memcpy(w, c.blk + q, 16);
-                } else {
-                    const uint4 t = load16_tail(c.blk, q, c.in_len);
-                    w[0] = t.x;
-                    w[1] = t.y;
-                    w[2] = t.z;
-                    w[3] = t.w;
-                }
-                coff = w[0] & 0xFFFFu;
-                q += 2;
-                cml = tok & 15;
-                if (cml == 15) {
-                    bool run = true;
-                    for (int t = 2; t < 16 && run; ++t) {
-                        const uint32_t wd = t < 4 ? w[0] : t < 8 ? w[1] : t < 12 ? w[2] : w[3];
-                        const uint32_t b = (wd >> (8 * (t & 3))) & 255u;
-                        cml += b;
-                        ++q;
-                        run = b == 255;
-                    }
-                    if (run) cml += wave_varint(c, lane, q);
-                }
-                cml += 4;
-            }
-            cq = q;
-        }
-        const int64_t tab_hi = c.O + total;
-        if (XP && xp) {
-            // export the sequences whose tokens lie in [seg_lo, seg_hi); the first one found is
-            // the segment's entry, the first at or past seg_hi its exit
-            const uint32_t ipc = (uint32_t)c.ip;
-            const uint32_t ntot = nseq + (cut ? 1u : 0u);   // the cut sequence is number nseq
-            const uint32_t ecut = cut ? seq_err<XP>(c, true, tab_hi, clit, cll, coff, cml) : 0u;
-            const uint32_t ferr = first_err != 0xFFFFFFFFu ? first_err : (ecut ? ((nseq << 3) | ecut) : 0xFFFFFFFFu);
-            const uint32_t fk = ferr == 0xFFFFFFFFu ? ntot : (ferr >> 3);
-            auto x_tok = [&](uint32_t k) -> uint32_t {   // token position (block-relative)
-                if (k >= nseq) return ipc + last_tok;
-                const SeqInfo q = seq_info(S, k);
-                return ipc + (uint32_t)q.lit - 1u - (q.ll >= 15 ? (uint32_t)(q.ll - 15) / 255u + 1u : 0u);
-            };
-            auto x_out = [&](uint32_t k) -> int64_t { return k >= nseq ? tab_hi : (int64_t)S.t_seq[k].x; };
-            uint32_t k0 = ntot, k1 = ntot;
-            for (uint32_t r = 0; 64u * r < ntot; ++r) {
-                const uint32_t k = 64u * r + lane;
-                const uint32_t t = k < ntot ? x_tok(k) : 0xFFFFFFFFu;
-                const uint64_t m0 = __ballot(k < ntot && t >= seg_lo), m1 = __ballot(k < ntot && t >= seg_hi);
-                if (k0 == ntot && m0) k0 = 64u * r + (uint32_t)__builtin_ctzll(m0);
-                if (k1 == ntot && m1) k1 = 64u * r + (uint32_t)__builtin_ctzll(m1);
-            }
-            bool restart = false;
-            if (!x_started && fk < k0) {
-                // an error before the segment: a wrong walk, or an earlier segment's error (which
-                // that segment's parse reports) -- never this segment's. A guess starts over one
-                // byte past the impossible token (text: an offset of 0 read from the wrong bytes
-                // failed 22 of a 4 MiB block's 255 guesses, which then waited for re-parses)
-                if (x_pass == 0 && x_restart < kSegRestarts) {
-                    restart = true;
-                    ++x_restart;
-                } else {
-                    x_fail = x_done = true;
-                }
-            } else {
-                if (!x_started && k0 < ntot) {
-                    x_started = true;
-                    x_G = x_tok(k0);
-                    x_OG = x_out(k0);
-                }
-                if (x_started) {
-                    const uint32_t ke = fk < k1 ? fk + 1 : k1;   // with the failing one (checks 1, 4, 5)
-                    for (uint32_t k = k0 + lane; k < ke; k += kWave) {
-                        uint4 e;
-                        if (k < nseq) {
-                            const SeqInfo q = seq_info(S, k);
-                            e = make_uint4((uint32_t)(x_out(k) - x_OG), ipc + (uint32_t)q.lit, (uint32_t)q.ll,
-                                           q.ml ? (uint32_t)q.off : 0u);
-                        } else {
-                            e = make_uint4((uint32_t)(tab_hi - x_OG), (uint32_t)clit, (uint32_t)cll, cml ? coff : 0u);
-                        }
-                        xs[nx + (k - k0)] = e;
-                    }
-                    if (fk < k1) {
-                        x_err = ((nx + (fk - k0)) << 3) | (ferr & 7u);
-                        x_done = true;
-                    } else if (k1 < ntot) {
-                        x_done = true;
-                        x_X = x_tok(k1);
-                        x_olen = (uint32_t)(x_out(k1) - x_OG);
-                    }
-                    nx += ke - k0;
-                }
-            }
-            if (restart) {
-                c.ip = (int32_t)(x_tok(fk) + 1u);
-                c.O = 0;
-            } else if (!x_done) {   // on to the next chunk
-                if (cut) {
-                    c.O = tab_hi + cll + cml;
-                    c.ip = (int32_t)(cq < c.in_len ? cq : c.in_len);
-                } else {
-                    c.O = tab_hi;
-                    c.ip = tail >= kEnd ? c.in_len : c.ip + (int32_t)tail;
-                }
-                if ((uint32_t)c.ip >= seg_hi && c.ip < c.in_len) {   // the chain leaps the segment's end
-                    if (!x_started) {
-                        x_started = true;
-                        x_G = (uint32_t)c.ip;
-                        x_OG = c.O;
-                    }
-                    x_done = true;
-                    x_X = (uint32_t)c.ip;
-                    x_olen = (uint32_t)(c.O - x_OG);
-                }
-            }
+        if (kParseOnly) {
+            c.ip = P.tail == kEnd ? c.in_len : c.ip + (P.cut ? kChunk : (int32_t)P.tail);
             __syncthreads();
             continue;
         }
-        if (cut) {   // the next chunk's bytes: their loads go out before this chunk's stores
-            int64_t nip = cq < c.in_len ? cq : c.in_len;
-            if (nip < c.in_len) {
-                    pf0 = stage_piece(c, nip + 16 * opaque(lane));
-                if (lane < kStageWords / 4 - kWave) pf1 = stage_piece(c, nip + 16 * (kWave + opaque(lane)));
-                    pf_at = nip;
-                have_pf = true;
-            }
-        }
-
-#if LZ4MI_ABLATE == 0 || LZ4MI_ABLATE >= 4
-        PROF(4);
-        __builtin_amdgcn_s_setprio(3);
-        // ---- 5. output rounds ---------------------------------------------
-        // The previous chunk's stores (read back as history below) and the next
-        // chunk's loads are complete: the stores had the whole parse to drain.
-        wait_vmem();
-        settle(pf0);    // (so the next chunk's stage does not wait for this chunk's stores)
-        settle(pf1);
-        PROF(21);
-        // output -> sequence map for remap_src, in the (now idle) next-token table
-        // output -> sequence map granule: 32 bytes for long sequences (tiles216: 16 B costs 1.8 %),
-        // 16 for short ones (text: 32 B costs 6 %, more sequences per granule to step over)
-        uint32_t msh = total >= 32u * nseq ? 5u : 4u;
-        while ((total >> msh) >= kLim) ++msh;
-        for (uint32_t k = lane; k < nseq; k += kWave) {
-            const uint32_t t0 = S.t_seq[k].x - (uint32_t)c.O;
-            const uint32_t t1 = (k + 1 < nseq ? S.t_seq[k + 1].x : (uint32_t)(c.O + total)) - (uint32_t)c.O;
-            for (uint32_t b = (t0 + (1u << msh) - 1) >> msh; (b << msh) < t1; ++b) S.nxt[b] = (uint16_t)k;
-        }
-        __syncthreads();
-        PROF(22);
-        uint32_t pend = 0;    // bit i: the match of sequence 64i+lane is still to be written
-        uint32_t ready = 0;   // bit i: ... is written by this lane in this round
-        uint32_t rbits = 0;   // bit i: ... reads a remapped source (SeqInfo::rsrc)
-        uint32_t nlit_pack = 0;   // byte i (rows < 4): literal prefix of a split match (remap_src 3)
-        for (uint32_t i = 0; 64 * i < nseq; ++i) {            // round 1
-            const uint32_t k = 64 * i + lane;
-            Run M = no_run(), ML = no_run();
-            SeqInfo q = seq_info(S, k < nseq ? k : 0u);
-            if (k >= nseq) q.ll = 0;
-            {   // the literal runs first (their registers are free before the remap)
-                const Run L = q.ll ? Run{q.out, q.ll, q.lit, 0, R_LDS} : no_run();
-                const bool longL = L.n > kLaneBytes;
-                lane_literals(c, S, longL ? no_run() : L);
-                for (uint64_t lm = __ballot(longL); lm; lm &= lm - 1) wave_run(c, S, lane, shfl_run(L, __builtin_ctzll(lm)), no_pat());
-            }
-            PROF(23);
-            if (k < nseq) {
-                const int32_t t0 = q.out;
-                M = match_run(c, t0 + q.ll, q.off, q.ml);
-                if (M.n == 0) {
-                    M.kind = R_NONE;
-                } else if (match_src_end(M) > (int32_t)c.O) {
-                    // the source is output of this table: map it back through the
-                    // sequences that wrote it, else wait for a later round
-                    int32_t rs = M.src, re = match_src_end(M), li = 0, nl = 0;
-                    const int r = (M.kind == R_HIST && M.period == 0)
-                                      ? remap_src(c, S, nseq, msh, rs, re, li, nl, i < 4)
-                                      : 0;
-                    if (r == 3) {   // literal prefix from the stage, the rest from finished output
-                        ML = Run{M.y, nl, li, 0, R_LDS};
-                        M.y += nl;
-                        M.n -= nl;
-                        nlit_pack |= (uint32_t)nl << (8 * i);
-                    }
-                    if (r == 1 || r == 3) {
-                        M.src = rs;
-                        if (c.out_off + rs < 16) M.kind = R_BYTES;
-                        S.t_seq[k].w = (uint32_t)(rs + (r == 3 ? kSplitBase : kMemoBase));
-                        rbits |= 1u << i;
-                    } else if (r == 2) {
-                        ML = Run{M.y, M.n, li, 0, R_LDS};
-                        M.kind = R_NONE;
+        if (T.first_err != 0xFFFFFFFFu && !xp) { status = err_status(T.first_err & 7); break; }
+        PROF(3);
+        CutSeq cs;                                                          // 5
+        {
+            const uint8_t* s = (const uint8_t*)S.stage;
+            int64_t cq = 0, cll = 0, cml = 0, clit = 0;
+            uint32_t coff = 0;
+            if (P.cut) {
+                // token and literal length from the staged bytes while they last
+                constexpr uint32_t kStaged = 16 * (kStageWords / 4);
+                uint32_t r = P.last_tok;
+                const uint32_t tok = s[r++];
+                cll = tok >> 4;
+                bool more = cll == 15;
+                while (more && r < kStaged) {
+                    const uint32_t b = s[r++];
+                    cll += b;
+                    more = b == 255;
+                }
+                int64_t q = (int64_t)c.ip + r;
+                if (more) cll += wave_varint(c, lane, q);
+                clit = q;
+                q += cll;
+                if (q < c.in_len) {
+                    // offset and match length: one 16-byte load covers them unless the length runs on
+                    uint32_t w[4];
+                    if (q + 16 <= c.in_len) {
+                        __builtin_memcpy(w, c.blk + q, 16);
                     } else {
-                        pend |= 1u << i;
-                        M.kind = R_NONE;
+                        const uint4 t = load16_tail(c.blk, q, c.in_len);
+                        w[0] = t.x;
+                        w[1] = t.y;
+                        w[2] = t.z;
+                        w[3] = t.w;
                     }
-                }
-            }
-            const bool longM = M.kind != R_NONE && M.n > kLaneBytes;
-            const bool longML = ML.n > kLaneBytes;
-            const bool fastM = M.kind == R_HIST && M.period == 0 && M.n >= 16;
-            if (M.kind != R_NONE && !longM && fastM) ready |= 1u << i;
-            PROF(16);
-            lane_literals(c, S, longML ? no_run() : ML);
-            PROF(17);
-            for (uint64_t lm = __ballot(longML); lm; lm &= lm - 1) wave_run(c, S, lane, shfl_run(ML, __builtin_ctzll(lm)), no_pat());
-            if (M.kind != R_NONE && !longM && !fastM) lane_slow_run(c, S, M);
-            for (uint64_t mm = __ballot(longM); mm; mm &= mm - 1) wave_run(c, S, lane, shfl_run(M, __builtin_ctzll(mm)), pat_round1(S));
-            PROF(18);
-        }
-        piece_pipe(c, S, ready, rbits, lane, nseq, nlit_pack);
-        PROF(19);
-        for (; LZ4MI_ABLATE != 6;) {                           // rounds 2, 3, ...
-            uint32_t np = 0;
-            for (uint32_t i = 0; 64 * i < nseq; ++i) {
-                const bool pk = (pend >> i) & 1u;
-                const uint64_t bal = __ballot(pk);
-                if (pk) {
-                    const uint32_t k = 64 * i + lane;
-                    const uint32_t idx = np + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
-                                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                    const SeqInfo q = seq_info(S, k);
-                    const int32_t ms = q.out + q.ll;
-                    S.pms[idx] = (uint32_t)ms;
-                    S.pme[idx] = (uint32_t)(ms + q.ml > c.cap ? c.cap : ms + q.ml);
-                }
-                np += (uint32_t)__popcll(bal);
-            }
-            if (np == 0) break;
-            PROF_COUNT(11, 1);
-            __syncthreads();
-            wait_vmem();      // the previous round's stores are complete
-            PROF(20);
-            ready = 0;
-            for (uint32_t i = 0; 64 * i < nseq; ++i) {
-                if (__ballot((pend >> i) & 1u) == 0) continue;
-                Run M = no_run();
-                if ((pend >> i) & 1u) {
-                    const uint32_t k = 64 * i + lane;
-                    const SeqInfo q = seq_info(S, k);
-                    M = match_run(c, q.out + q.ll, q.off, q.ml);
-                    // first pending match ending past the source start: ready if it starts at or past the source end
-                    const int32_t rs = M.src, re = match_src_end(M);
-                    uint32_t lo = 0, hi = np;
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if ((int32_t)S.pme[mid] > rs) hi = mid;
-                        else lo = mid + 1;
+                    coff = w[0] & 0xFFFFu;
+                    q += 2;
+                    cml = tok & 15;
+                    if (cml == 15) {
+                        bool run = true;
+                        for (int t = 2; t < 16 && run; ++t) {
+                            const uint32_t wd = t < 4 ? w[0] : t < 8 ? w[1] : t < 12 ? w[2] : w[3];
+                            const uint32_t b = (wd >> (8 * (t & 3))) & 255u;
+                            cml += b;
+                            ++q;
+                            run = b == 255;
+                        }
+                        if (run) cml += wave_varint(c, lane, q);
                     }
-                    if (lo >= np || (int32_t)S.pms[lo] >= re) pend &= ~(1u << i);
-                    else M.kind = R_NONE;
+                    cml += 4;
                 }
-                const bool longM = M.kind != R_NONE && M.n > kLaneBytes;
-                const bool fastM = M.kind == R_HIST && M.period == 0 && M.n >= 16;
-                if (M.kind != R_NONE && !longM && fastM) ready |= 1u << i;
-                if (M.kind != R_NONE && !longM && !fastM) lane_slow_run(c, S, M);
-                for (uint64_t mm = __ballot(longM); mm; mm &= mm - 1) wave_run(c, S, lane, shfl_run(M, __builtin_ctzll(mm)), pat_rounds(S));
+                cq = q;
             }
-            piece_pipe(c, S, ready, 0u, lane, nseq, 0u);
-            __syncthreads();
+            cs = CutSeq{cq, cll, cml, clit, coff};
         }
-        PROF(6);
-        if (cut) {
-            PROF_COUNT(12, 1);
-            const uint32_t e = seq_error(c, tab_hi, clit, cll, coff, cml);
+        if constexpr (XP) {
+            if (xp) {
+                x_export_chunk(c, S, x, lane, P, T, cs);
+                continue;
+            }
+        }
+        const int64_t tab_hi = c.O + T.total;
+        // after a cut sequence, the next chunk's bytes: their loads go out before this chunk's stores
+        if (P.cut && cs.cq < c.in_len) prefetch(c, pf, cs.cq, lane);
+        if (kOutput) {                                                      // 6
+            PROF(4);
+            __builtin_amdgcn_s_setprio(3);
+            // The previous chunk's stores (read back as history below) and the next
+            // chunk's loads are complete: the stores had the whole parse to drain.
+            wait_vmem();
+            settle(pf);
+            PROF(21);
+            output_rounds(c, S, lane, T, prof);
+            PROF(6);
+        }
+        if (P.cut) {   // its checks, then its literal run; its match after the table's F1 replay
+            if (kOutput) PROF_COUNT(12, 1);
+            const uint32_t e = seq_error(c, tab_hi, cs.clit, cs.cll, cs.coff, cs.cml);
             if (e) { status = err_status(e); break; }
-            wave_run(c, S, lane, Run{(int32_t)tab_hi, (int32_t)cll, (int32_t)clit, 0, cll ? (uint32_t)R_COMP : (uint32_t)R_NONE}, no_pat());
+            if (kOutput)
+                wave_run(c, S, lane, Run{(int32_t)tab_hi, (int32_t)cs.cll, (int32_t)cs.clit, 0, cs.cll ? (uint32_t)R_COMP : (uint32_t)R_NONE}, no_pat());
         }
-#else
-        if (cut) {
-            const uint32_t e = seq_error(c, tab_hi, clit, cll, coff, cml);
-            if (e) { status = err_status(e); break; }
-        }
-#endif
         PROF(7);
-        if (a.f1check) {
-            // candidates first, from the sequence table alone (offset >= 8, length < 8): a chunk
-            // without one -- every tiles216 chunk -- neither drains its stores here nor reads
-            // them back, so they keep draining beside the next chunk's parse as in spec mode
-            bool cand = false;
-            for (uint32_t k = lane; k < nseq; k += kWave) {
-                const SeqInfo q = seq_info(S, k);
-                cand |= q.ml != 0 && q.ml < 8 && q.off >= 8;
-            }
-            if (__ballot(cand)) {
-                wait_vmem();    // this chunk's stores are complete before they are read back
-                uint32_t dv = 0;
-                for (uint32_t k = lane; k < nseq; k += kWave) {
-                    const SeqInfo q = seq_info(S, k);
-                    dv |= f1_changes(c, q.out + q.ll, q.off, q.ml);
-                }
-                if (__ballot(dv & 2u)) { status = -9; break; }
-                if (__ballot(dv)) f1_fixup(c, S, lane, nseq, false, 0, 0, 0);
-            }
+        if (a.f1check) {                                                    // 7
+            status = f1_table(c, S, lane, T.nseq);
+            if (status) break;
         }
-#if LZ4MI_ABLATE == 0 || LZ4MI_ABLATE >= 4
-        // the cut sequence's match, after the table's F1 replay (it reads the replayed
-        // bytes, as the reference's copy does); the tables are idle now: all of LDS
-        // can hold a periodic pattern
-        if (cut) {
-            const Run M = match_run(c, (int32_t)(tab_hi + cll), (int32_t)coff, (int32_t)cml);
-            if (M.n > 0) {
-                wait_vmem();    // everything below the match is read back as history
-                wave_run(c, S, lane, M, pat_all(S));
-            }
-            if (a.f1check && cml != 0 && cml < 8 && coff >= 8) {    // its own tail rewrite, after its copy as in the reference
-                wait_vmem();
-                const uint32_t dv = lane == 0 ? f1_changes(c, (int32_t)(tab_hi + cll), (int32_t)coff, (int32_t)cml) : 0u;
-                if (__ballot(dv & 2u)) { status = -9; break; }
-                if (__ballot(dv)) f1_fixup(c, S, lane, 0, true, (int64_t)(tab_hi + cll), (int32_t)coff, (int32_t)cml);
-            }
+        if (kOutput && P.cut) {
+            status = cut_match(c, S, lane, (int32_t)(tab_hi + cs.cll), cs, a.f1check);
+            if (status) break;
         }
-#endif
-        c.O = tab_hi;
-        if (cut) {
-            c.O += cll + cml;
-            c.ip = (int32_t)(cq < c.in_len ? cq : c.in_len);
-        } else if (tail >= kEnd) {
-            c.ip = c.in_len;
-        } else {
-            c.ip += (int32_t)tail;
-        }
+        advance(c, tab_hi, P, cs);
         __syncthreads();
         PROF(8);
     }
-    if (XP && xp) {
-        if (!x_done) {   // the block's end
-            if (!x_started) {
-                x_G = (uint32_t)c.in_len;
-                x_OG = c.O;
-            }
-            x_X = (uint32_t)c.in_len;
-            x_olen = (uint32_t)(c.O - x_OG);
-        }
-        if (lane == 0) {
-            xr->entry = x_G;
-            xr->exit = x_X;
-            xr->cnt = nx;
-            xr->olen = x_olen;
-            xr->err = x_err;
-            xr->fail = (x_fail || (a.xforce && sg > 0 && (a.xforce == 2 ? x_pass != 1 : x_pass == 0))) ? 1u : 0u;
-            if (x_pass == 1)   // the exact re-parse of phase 1: final
-                __hip_atomic_store(&xr->fin, (x_err != 0xFFFFFFFFu ? kFinErr : x_X) + 1u, __ATOMIC_RELEASE,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
+    if constexpr (XP) {
+        if (xp) {
+            x_finish(a, c, x, lane, sg);
 #if LZ4MI_LL_ADAPT
-        if (lat_bound && lane == 0) atomicSub(lat, 1u);
+            if (lat_bound && lane == 0) atomicSub(lat, 1u);
 #endif
-        return;   // status and length: lz4mi_xcheck_kernel
+            return;   // status and length: lz4mi_xcheck_kernel
+        }
     }
 #if LZ4MI_PROFILE
     if (lane == 0)
-        for (int i = 0; i < 24; ++i) atomicAdd(&g_prof[i], (unsigned long long)prof[i]);
+        for (int i = 0; i < 24; ++i) atomicAdd(&g_prof[i], (unsigned long long)prof.acc[i]);
 #endif
     if (lane == 0) {
         a.status[b] = status;

@@ -160,6 +160,32 @@ def cases_slow():
     return out
 
 
+def cases_redo():
+    """The fast next-token table sent back for the exact one: a match length field of 2 bytes and
+    one of 3 bytes among the true tokens of one chunk, far enough from the block's end for the
+    fast table. redo_2k: in the first chunk of a block of about 2 KiB (one segment). redo_seg1:
+    past 5120 compressed bytes in a block of two segments, so that segment 1's parse -- the guess
+    and, forced, the re-parse from segment 0's exit -- meets them too."""
+    long2, long3 = 4 + 15 + 255 + 40, 4 + 15 + 600
+    m = Maker(600)
+    a = m.short(10) + [m.seq(2, long2)] + m.short(20) + [m.seq(1, long3)] + m.short(470)
+    fa = m.lits(5)
+    m = Maker(601)
+    b = m.short(1300) + [m.seq(2, long2)] + m.short(20) + [m.seq(1, long3)] + m.short(1000)
+    return {"redo_2k": (a, fa), "redo_seg1": (b, m.lits(5))}
+
+
+@functools.lru_cache(maxsize=None)
+def redo_cases():
+    done = {}
+    for name, (s, f) in cases_redo().items():
+        comp = encode(s, f)
+        st, cap, _ = O.decompress_block(comp, 1 << 16)
+        assert st == 0 and cap <= (1 << 16), name
+        done[name] = (comp, cap, {js: O.decompress_block(comp, cap, js_compat=js) for js in (False, True)})
+    return done
+
+
 def build_cases():
     """name -> (compressed block, capacity, dictionary or None)."""
     cases = {}
@@ -267,6 +293,26 @@ def test_cases_are_what_they_claim():
     assert max(cs[f"fuzz{i}"][0].size for i in range(200)) <= 8192
 
 
+def test_redo_cases_are_what_they_claim():
+    """CPU: the long match length fields lie where the fast table is in use (more than
+    kFastRem = 1024 + 64 + 300 bytes before the block's end), in the first chunk of a one-segment
+    block and in segment 1 (from 5120) of a two-segment one (csrc/lz4mi_decompress.h, seg_geom)."""
+    cs = redo_cases()
+    comp = cs["redo_2k"][0]
+    two, three = 4 * 10, 4 * 10 + 3 + 2 + 2 + 4 * 20      # tokens of the two long matches
+    assert 2 * CHUNK - 100 <= comp.size <= 8192 and three < CHUNK
+    assert comp[two] & 15 == 15 and list(comp[two + 5:two + 7]) == [255, 40]
+    assert comp[three] & 15 == 15 and list(comp[three + 4:three + 7]) == [255, 255, 90]
+    comp = cs["redo_seg1"][0]
+    two = 4 * 1300
+    three = two + 3 + 2 + 2 + 4 * 20
+    assert 8192 < comp.size <= 16384 and two >= 5120 and comp.size - three > 2 * CHUNK
+    assert comp[two] & 15 == 15 and list(comp[two + 5:two + 7]) == [255, 40]
+    assert comp[three] & 15 == 15 and list(comp[three + 4:three + 7]) == [255, 255, 90]
+    for name, (comp, cap, ref) in cs.items():
+        assert ref[False][0] == 0 and ref[True][0] == 0, name
+
+
 def _check(lz4mi, name, comp, cap, ref, js, st, out, n, batched_at=None):
     """One decoded block against the oracle; batched_at: the block's output offset in a batch of
     independent blocks, where a reference before the block's start is CROSS_BLOCK."""
@@ -300,6 +346,28 @@ def test_small_batch_path(js):
         st, outs, lens = lz4mi.decompress_blocks([comp] * 3, [cap] * 3, js_exact=js)
         for j in range(3):
             _check(lz4mi, name, comp, cap, ref, js, st[j], outs[j], lens[j], batched_at=j * cap)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("js", [False, True], ids=["spec", "js_exact"])
+@pytest.mark.parametrize("path", ["batch", "small_reparse"])
+def test_fast_table_redo(path, js, monkeypatch):
+    """A true token's match length field of 2 and of 3 bytes where the fast next-token table is in
+    use: the chunk is parsed again with the exact table (decompress_block's loop around
+    parse_chunk and seq_table). Both instantiations that take that path: the batch kernel
+    (SMALL_BLOCKS + 8 copies) and the small path's export kernel, one block, with the test hook
+    LZ4MI_SMALL_REPARSE=2 (every guess past segment 0 counts as wrong, so redo_seg1's segment 1 is
+    parsed again from segment 0's exit)."""
+    lz4mi = pytest.importorskip("lz4mi")
+    lz4mi.init(0)
+    if path == "small_reparse":
+        monkeypatch.setenv("LZ4MI_SMALL_REPARSE", "2")
+    copies = lz4mi.SMALL_BLOCKS + 8 if path == "batch" else 1
+    for name, (comp, cap, ref) in redo_cases().items():
+        st, outs, lens = lz4mi.decompress_blocks([comp] * copies, [cap] * copies, js_exact=js)
+        for j in range(copies):
+            _check(lz4mi, name, comp, cap, ref, js, st[j], outs[j], lens[j],
+                   batched_at=j * cap if copies > 1 else None)
 
 
 @pytest.mark.gpu
