@@ -309,17 +309,22 @@ struct StagedIn {
     std::vector<uint64_t> h_in_off;   // the host's copy of in_off
     const uint32_t* h_in_len;
     uint32_t nblocks;
+    uint64_t total;                   // bytes of g_ctx.in the blocks take
     uint8_t* in;
     uint64_t *in_off, *more64;
     uint32_t *in_len, *more32;
 
+    // own_bytes (lz4mi_verify_blocks): the bytes to stage per block instead of the rule above
     int32_t copy(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len, uint32_t n, bool frame_words,
-                 uint32_t n64, uint32_t n32, hipStream_t s) {
-        auto bytes = [&](uint32_t b) -> uint64_t { return (frame_words && (src_len[b] & 0x80000000u)) ? 0 : src_len[b]; };
+                 uint32_t n64, uint32_t n32, hipStream_t s, const uint64_t* own_bytes = nullptr) {
+        auto bytes = [&](uint32_t b) -> uint64_t {
+            if (own_bytes) return own_bytes[b];
+            return (frame_words && (src_len[b] & 0x80000000u)) ? 0 : src_len[b];
+        };
         h_in_len = src_len;
         nblocks = n;
         h_in_off.resize(n);
-        uint64_t total = 0;
+        total = 0;
         for (uint32_t b = 0; b < n; ++b) {
             h_in_off[b] = total;
             total += round16(bytes(b));
@@ -816,6 +821,52 @@ int32_t lz4mi_xxh32_blocks(const uint8_t* in, const uint64_t* off, const uint32_
     return LZ4MI_OK;
 }
 
+int32_t lz4mi_host_verify_blocks(const uint8_t* in, uint64_t in_total, const uint64_t* in_off, const uint32_t* in_len,
+                                 int32_t* status, uint32_t nblocks, uint32_t flags) {
+    if (flags & ~LZ4MI_FRAME_WORDS) return LZ4MI_ERR_ARG;
+    if (!status || ((!in || !in_off || !in_len) && nblocks)) return LZ4MI_ERR_ARG;
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        const uint64_t n = (flags & LZ4MI_FRAME_WORDS) ? in_len[b] & 0x7FFFFFFFu : in_len[b];
+        const bool whole = in_off[b] <= in_total && n + 4 <= in_total - in_off[b];
+        const uint8_t* p = in + in_off[b];
+        status[b] = whole && lz4mi_xxh32(p, n, 0, LZ4MI_XXH_STANDARD) == le32(p + n) ? LZ4MI_OK : LZ4MI_ERR_BLOCK_CHECKSUM;
+    }
+    return LZ4MI_OK;
+}
+
+int32_t lz4mi_verify_blocks(const uint8_t* in, uint64_t in_total, const uint64_t* in_off, const uint32_t* in_len,
+                            int32_t* status, uint32_t nblocks, uint32_t flags, void* stream) {
+    if (flags & ~(LZ4MI_DEVICE_PTRS | LZ4MI_FRAME_WORDS)) return LZ4MI_ERR_ARG;
+    if (!status || ((!in || !in_off || !in_len) && nblocks)) return LZ4MI_ERR_ARG;
+    DeviceGuard dg;
+    if (dg.status()) return dg.status();
+    if (nblocks == 0) return LZ4MI_OK;
+    const int fw = (flags & LZ4MI_FRAME_WORDS) ? 1 : 0;
+    if (flags & LZ4MI_DEVICE_PTRS) {   // no scratch: nothing to lock
+        LZ4MI_TRY(lz4mi_launch_verify(in, in_total, in_off, in_len, status, nblocks, fw, pick_stream(stream)));
+        return LZ4MI_OK;
+    }
+    // every whole record's payload and the four bytes behind it; a record the end cuts stages nothing and
+    // is placed at the end of what was staged, where the kernel finds it cut as well
+    std::vector<uint64_t> rec(nblocks);
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        const uint64_t n = fw ? in_len[b] & 0x7FFFFFFFu : in_len[b];
+        rec[b] = (in_off[b] <= in_total && n + 4 <= in_total - in_off[b]) ? n + 4 : 0;
+    }
+    std::lock_guard<std::mutex> lk(g_ctx.mu);
+    hipStream_t s = g_ctx.stream;
+    StagedIn st;   // meta: in_off, in_len, status
+    if (int32_t e = st.copy(in, in_off, in_len, nblocks, fw != 0, 0, 1, s, rec.data())) return e;
+    for (uint32_t b = 0; b < nblocks; ++b)
+        if (!rec[b]) st.h_in_off[b] = st.total;
+    if (int32_t e = st.upload(nullptr, s)) return e;
+    int32_t* m_status = (int32_t*)st.more32;
+    LZ4MI_TRY(lz4mi_launch_verify(st.in, st.total, st.in_off, st.in_len, m_status, nblocks, fw, s));
+    LZ4MI_TRY(hipMemcpyAsync(status, m_status, 4ull * nblocks, hipMemcpyDeviceToHost, s));
+    LZ4MI_TRY(hipStreamSynchronize(s));
+    return LZ4MI_OK;
+}
+
 int32_t lz4mi_frame_pack(const uint8_t* raw, const uint64_t* raw_off, const uint32_t* raw_len, const uint8_t* comp,
                          const uint64_t* comp_off, const uint32_t* comp_len, uint8_t* frame, const uint64_t* rec_off,
                          uint32_t nblocks, uint32_t flags, void* stream) {
@@ -885,7 +936,7 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     std::lock_guard<std::mutex> sl(c->mu);
     const size_t per = 8 + 4 + 8 + 4 + 4;   // compressed lists (in_off, in_len, out_off, out_cap, idx)
     const size_t per_s = 8 + 4 + 8 + 4;     // stored lists (in_off, len, out_off, idx)
-    const size_t meta = cap_blocks * (per + per_s + 4 + 4) + 64 + 64;   // + out_len, status
+    const size_t meta = cap_blocks * (per + per_s + 4 + 4 + 4 + 4) + 64 + 64;   // + out_len, status, checksum statuses
     LZ4MI_TRY(c->scan.ensure(meta, s));
     uint8_t* m = c->scan.as<uint8_t>();
     int64_t* d_info = (int64_t*)m;
@@ -900,6 +951,8 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     uint32_t* s_idx = s_len + cap_blocks;
     uint32_t* d_out_len = s_idx + cap_blocks;
     int32_t* d_status = (int32_t*)(d_out_len + cap_blocks);
+    int32_t* c_sum = d_status + cap_blocks;   // LZ4MI_VERIFY_BLOCKS: the block checksums' statuses, per list
+    int32_t* s_sum = c_sum + cap_blocks;
     LZ4MI_TRY(lz4mi_launch_frame_scan(frame, len, (uint32_t)cap_blocks, c_in_off, c_in_len, c_out_off, c_out_cap,
                                       s_in_off, s_len, s_out_off, c_idx, s_idx, d_info, s));
     int64_t hi[8];
@@ -910,6 +963,13 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     if (hi[2] <= 0 || hi[7]) return LZ4MI_ERR_ARG;     // no content size, or not the reference's layout: host path
     if ((uint64_t)hi[2] > out_cap) return LZ4MI_ERR_ARG;
     const uint32_t nc = (uint32_t)hi[3], ns = (uint32_t)hi[4];
+    // LZ4MI_VERIFY_BLOCKS on a frame with block checksums (FLG 0x10): both lists' payloads against the four
+    // bytes behind them; the statuses come back with the lists below
+    const bool sums = (flags & LZ4MI_VERIFY_BLOCKS) && (hi[1] & 0x10);
+    if (sums) {
+        LZ4MI_TRY(lz4mi_launch_verify(frame, len, c_in_off, c_in_len, c_sum, nc, 0, s));
+        LZ4MI_TRY(lz4mi_launch_verify(frame, len, s_in_off, s_len, s_sum, ns, 0, s));
+    }
     // stored blocks, then every compressed block in one batch (spec or reference-exact)
     LZ4MI_TRY(lz4mi_launch_frame_stored(frame, len, s_in_off, s_len, s_out_off, out, (uint64_t)hi[2], ns, s));
     // (LZ4MI_LINKED: after the stored copies, the compressed blocks in one linked call -- their slots ascend in
@@ -919,7 +979,7 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     if (nc && linked) LZ4MI_TRY(linked_launch(cb, 0, lx ? 1 : 0, s, &c->small, (uint32_t)bmax, (uint32_t)bmax));
     else if (nc) LZ4MI_TRY(decode_launch(cb, mode, s, &c->order));
     std::vector<uint32_t> olen(nc), cap(nc), cidx(nc), slen(ns), sidx(ns);
-    std::vector<int32_t> stat(nc);
+    std::vector<int32_t> stat(nc), vsum(sums ? nc + ns : 0);
     std::vector<uint64_t> soff(ns), ooff(nc), ioff(nc);
     if (nc) {
         LZ4MI_TRY(hipMemcpyAsync(olen.data(), d_out_len, 4ull * nc, hipMemcpyDeviceToHost, s));
@@ -933,7 +993,18 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
         LZ4MI_TRY(hipMemcpyAsync(sidx.data(), s_idx, 4ull * ns, hipMemcpyDeviceToHost, s));
         LZ4MI_TRY(hipMemcpyAsync(soff.data(), s_out_off, 8ull * ns, hipMemcpyDeviceToHost, s));
     }
+    if (sums && nc) LZ4MI_TRY(hipMemcpyAsync(vsum.data(), c_sum, 4ull * nc, hipMemcpyDeviceToHost, s));
+    if (sums && ns) LZ4MI_TRY(hipMemcpyAsync(vsum.data() + nc, s_sum, 4ull * ns, hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipStreamSynchronize(s));
+    // a failing block checksum is the frame's error before any block's own (the JS layer's rule: every checksum
+    // is checked before a block is decoded) and before the layout checks below, which a damaged payload would
+    // fail as LZ4MI_ERR_ARG; what the decode launches wrote into out[0 .. content size) stays
+    for (const int32_t v : vsum)
+        if (v) {
+            info[0] = LZ4MI_ERR_BLOCK_CHECKSUM;
+            info[3] = 0;
+            return LZ4MI_OK;
+        }
     // blocks that read earlier blocks' output (dependent frames, or an F1 rewrite at a block start):
     // every block before them is final now; decode each alone, in order (LZ4MI_LINKED: nothing to do
     // unless a block failed or was refused -- the blocks from there on are resumed here)

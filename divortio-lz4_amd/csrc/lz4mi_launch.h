@@ -104,6 +104,8 @@ hipError_t lz4mi_launch_compress_chain(const uint8_t* src, uint64_t src_total, i
 hipError_t lz4mi_launch_xxh32(const uint8_t* in, const uint64_t* off, const uint32_t* len, uint32_t seed,
                               uint32_t* hashes, uint32_t n, int standard, uint8_t* dst, const uint64_t* dst_off,
                               hipStream_t stream);
+hipError_t lz4mi_launch_verify(const uint8_t* in, uint64_t in_total, const uint64_t* in_off, const uint32_t* in_len,
+                               int32_t* status, uint32_t n, int frame_words, hipStream_t stream);
 hipError_t lz4mi_launch_generate(uint8_t* out, uint32_t kind, uint32_t seed0, uint32_t bsize, uint32_t nblocks,
                                  hipStream_t stream);
 

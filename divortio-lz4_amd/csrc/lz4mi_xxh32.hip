@@ -17,12 +17,75 @@
 namespace lz4mi {
 
 constexpr uint32_t P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
+constexpr int32_t kErrBlockChecksum = -10;   // LZ4MI_ERR_BLOCK_CHECKSUM (include/lz4mi.h)
 
 __device__ __forceinline__ uint32_t rotl(uint32_t x, int r) { return __builtin_amdgcn_alignbit(x, x, 32 - r); }
 
 __device__ __forceinline__ uint32_t load_le32(const uint8_t* p, bool aligned) {
     if (aligned) return *(const uint32_t*)p;
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+// The stripe chain of one quad lane, shared by every kernel below so that they cannot drift:
+// v folded over this lane's dword (at q + 16 k) of stripes [0, stripes); `load` reads one LE32.
+// Software pipeline: the next kDepth stripes' words are in flight while the current kDepth are
+// folded into the accumulator (one load round trip per 2 x kDepth stripes would otherwise stall
+// the serial chain every kDepth steps). Nothing outside the stripes' own bytes is read.
+template <class Load>
+__device__ __forceinline__ uint32_t stripe_chain(uint32_t v, const uint8_t* q, uint64_t stripes, Load load) {
+    uint64_t k = 0;
+    constexpr int kDepth = 128;
+    if (stripes >= 2 * kDepth) {
+        uint32_t w[kDepth];
+#pragma unroll
+        for (int u = 0; u < kDepth; ++u) w[u] = load(q + 16 * u);
+        for (; k + 2 * kDepth <= stripes; k += kDepth) {
+            uint32_t nw[kDepth];
+#pragma unroll
+            for (int u = 0; u < kDepth; ++u) nw[u] = load(q + 16 * (k + kDepth + u));
+#pragma unroll
+            for (int u = 0; u < kDepth; ++u) v = rotl(v + w[u] * P2, 13) * P1;
+#pragma unroll
+            for (int u = 0; u < kDepth; ++u) w[u] = nw[u];
+        }
+#pragma unroll
+        for (int u = 0; u < kDepth; ++u) v = rotl(v + w[u] * P2, 13) * P1;
+        k += kDepth;
+    }
+    for (; k + 8 <= stripes; k += 8) {   // short buffers and the pipeline's remainder
+        uint32_t w[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) w[u] = load(q + 16 * (k + u));
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v = rotl(v + w[u] * P2, 13) * P1;
+    }
+    for (; k < stripes; ++k) v = rotl(v + load(q + 16 * k) * P2, 13) * P1;
+    return v;
+}
+
+// What lane 0 of a quad does with the quad's four accumulators: the convergence (`standard`: the
+// specification's), the length, the up to 15 bytes behind the last stripe and the avalanche.
+__device__ __forceinline__ uint32_t finish(uint32_t v1, uint32_t v2, uint32_t v3, uint32_t v4, const uint8_t* p,
+                                           uint64_t L, uint32_t seed, int standard) {
+    uint32_t h;
+    if (L >= 16) {
+        if (standard) {
+            h = rotl(v1, 1) + rotl(v2, 7) + rotl(v3, 12) + rotl(v4, 18);
+        } else {
+            h = rotl(v1, 1);
+            h = rotl(h + v2, 7);
+            h = rotl(h + v3, 12);
+            h = rotl(h + v4, 18);
+        }
+    } else {
+        h = seed + P5;
+    }
+    h += (uint32_t)L;
+    uint64_t pos = L >= 16 ? L / 16 * 16 : 0;
+    for (; pos + 4 <= L; pos += 4) h = rotl(h + load_le32(p + pos, false) * P3, 17) * P4;
+    for (; pos < L; ++pos) h = rotl(h + p[pos] * P5, 11) * P1;
+    h ^= h >> 15; h *= P2; h ^= h >> 13; h *= P3; h ^= h >> 16;
+    return h;
 }
 
 // hashes[buf] = digest; or (TO_FRAME) the digest stored little-endian at dst + dst_off[buf]
@@ -42,68 +105,64 @@ __global__ __launch_bounds__(256) void lz4mi_xxh32_kernel(const uint8_t* in, con
     const uint64_t stripes = L >= 16 ? L / 16 : 0;
 
     uint32_t init[4] = { seed + P1 + P2, seed + P2, seed, seed - P1 };
-    uint32_t v = init[j];
-    const uint8_t* q = p + 4 * j;
-    uint64_t k = 0;
-    // software pipeline: the next kDepth stripes' words are in flight while the
-    // current kDepth are folded into the accumulator (one load round trip per
-    // 2 x kDepth stripes would otherwise stall the serial chain every kDepth steps)
-    constexpr int kDepth = 128;
-    if (stripes >= 2 * kDepth) {
-        uint32_t w[kDepth];
-#pragma unroll
-        for (int u = 0; u < kDepth; ++u) w[u] = load_le32(q + 16 * u, aligned);
-        for (; k + 2 * kDepth <= stripes; k += kDepth) {
-            uint32_t nw[kDepth];
-#pragma unroll
-            for (int u = 0; u < kDepth; ++u) nw[u] = load_le32(q + 16 * (k + kDepth + u), aligned);
-#pragma unroll
-            for (int u = 0; u < kDepth; ++u) v = rotl(v + w[u] * P2, 13) * P1;
-#pragma unroll
-            for (int u = 0; u < kDepth; ++u) w[u] = nw[u];
-        }
-#pragma unroll
-        for (int u = 0; u < kDepth; ++u) v = rotl(v + w[u] * P2, 13) * P1;
-        k += kDepth;
-    }
-    for (; k + 8 <= stripes; k += 8) {   // short buffers and the pipeline's remainder
-        uint32_t w[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) w[u] = load_le32(q + 16 * (k + u), aligned);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v = rotl(v + w[u] * P2, 13) * P1;
-    }
-    for (; k < stripes; ++k) v = rotl(v + load_le32(q + 16 * k, aligned) * P2, 13) * P1;
+    const uint32_t v = stripe_chain(init[j], p + 4 * j, stripes,
+                                    [aligned](const uint8_t* a) { return load_le32(a, aligned); });
 
     // gather the quad's accumulators into every lane of the quad
     const int lane = threadIdx.x & 63, qb = lane & ~3;
     uint32_t v1 = __shfl(v, qb + 0, 64), v2 = __shfl(v, qb + 1, 64), v3 = __shfl(v, qb + 2, 64),
              v4 = __shfl(v, qb + 3, 64);
     if (!live || j != 0) return;
-    uint32_t h;
-    if (L >= 16) {
-        if (standard) {
-            h = rotl(v1, 1) + rotl(v2, 7) + rotl(v3, 12) + rotl(v4, 18);
-        } else {
-            h = rotl(v1, 1);
-            h = rotl(h + v2, 7);
-            h = rotl(h + v3, 12);
-            h = rotl(h + v4, 18);
-        }
-    } else {
-        h = seed + P5;
-    }
-    h += (uint32_t)L;
-    uint64_t pos = stripes * 16;
-    for (; pos + 4 <= L; pos += 4) h = rotl(h + load_le32(p + pos, false) * P3, 17) * P4;
-    for (; pos < L; ++pos) h = rotl(h + p[pos] * P5, 11) * P1;
-    h ^= h >> 15; h *= P2; h ^= h >> 13; h *= P3; h ^= h >> 16;
+    const uint32_t h = finish(v1, v2, v3, v4, p, L, seed, standard);
     if (TO_FRAME) {
         uint8_t* q8 = dst + dst_off[buf];
         for (int k = 0; k < 4; ++k) q8[k] = (uint8_t)(h >> (8 * k));
     } else {
         hashes[buf] = h;
     }
+}
+
+// Block checksums of a frame checked in place (lz4mi_verify_blocks): the same machine -- one quad
+// per block, 16 blocks per wave, the stripe chain above, spec convergence, seed 0 -- over block b's
+// payload in[in_off[b] .. +n), n = in_len[b] (frame_words: in_len[b] & 0x7FFFFFFF, a stored block's
+// raw bytes are a payload like any other); lane 0 of the quad compares the digest with the LE32
+// stored behind the payload and writes status[b] = 0 or LZ4MI_ERR_BLOCK_CHECKSUM. No digest is
+// written. Nothing outside in[0 .. in_total) is read: a record the end cuts (in_off[b] + n + 4 >
+// in_total) runs with length 0, reads nothing and gets LZ4MI_ERR_BLOCK_CHECKSUM.
+// Frame payloads start at any residue mod 4; a 4-byte memcpy compiles to one global_load_dword at
+// any alignment, so the lanes take no aligned / unaligned split.
+__global__ __launch_bounds__(256) void lz4mi_verify_kernel(const uint8_t* in, uint64_t in_total, const uint64_t* in_off,
+                                                           const uint32_t* in_len, int32_t* status, uint32_t n,
+                                                           int frame_words) {
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t buf = gid >> 2;
+    const int j = threadIdx.x & 3;
+    const bool live = buf < n;
+    const uint64_t at = live ? in_off[buf] : 0;
+    const uint32_t want = live ? (frame_words ? in_len[buf] & 0x7FFFFFFFu : in_len[buf]) : 0;
+    const bool whole = live && at <= in_total && (uint64_t)want + 4 <= in_total - at;
+    const uint8_t* p = whole ? in + at : nullptr;   // (nullptr: a cut record, or no block; with L = 0 never read)
+    const uint64_t L = whole ? want : 0;   // (64 bits as in the kernel above: the chain loop then gets its schedule)
+    const uint64_t stripes = L >= 16 ? L / 16 : 0;
+
+    constexpr uint32_t seed = 0;
+    uint32_t init[4] = { seed + P1 + P2, seed + P2, seed, seed - P1 };
+    const uint32_t v = stripe_chain(init[j], p + 4 * j, stripes, [](const uint8_t* a) {
+        uint32_t w;
+        __builtin_memcpy(&w, a, 4);
+        return w;
+    });
+
+    const int lane = threadIdx.x & 63, qb = lane & ~3;
+    uint32_t v1 = __shfl(v, qb + 0, 64), v2 = __shfl(v, qb + 1, 64), v3 = __shfl(v, qb + 2, 64),
+             v4 = __shfl(v, qb + 3, 64);
+    if (!live || j != 0) return;
+    int32_t st = kErrBlockChecksum;
+    if (p) {
+        const uint32_t h = finish(v1, v2, v3, v4, p, L, seed, 1);
+        if (h == load_le32(p + L, false)) st = 0;
+    }
+    status[buf] = st;
 }
 
 // ---------------------------------------------------------------------------
@@ -177,6 +236,16 @@ extern "C" hipError_t lz4mi_launch_xxh32(const uint8_t* in, const uint64_t* off,
     else
         hipLaunchKernelGGL(lz4mi::lz4mi_xxh32_kernel<false>, dim3((threads + 63) / 64), dim3(64), 0, stream, in, off,
                            len, seed, hashes, n, standard, dst, dst_off);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lz4mi_launch_verify(const uint8_t* in, uint64_t in_total, const uint64_t* in_off,
+                                          const uint32_t* in_len, int32_t* status, uint32_t n, int frame_words,
+                                          hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    // as lz4mi_launch_xxh32: one wave (16 blocks) per workgroup
+    hipLaunchKernelGGL(lz4mi::lz4mi_verify_kernel, dim3((n * 4 + 63) / 64), dim3(64), 0, stream, in, in_total, in_off,
+                       in_len, status, n, frame_words);
     return hipGetLastError();
 }
 

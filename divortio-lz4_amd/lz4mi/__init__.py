@@ -32,6 +32,7 @@ BLOCK_CHECKSUM = 0x20
 FRAME_WORDS = 0x40
 LINKED = 0x80
 LINKED_EXACT = 0x100
+VERIFY_BLOCKS = 0x200
 
 GEN_RANDOM, GEN_REPETITIVE, GEN_TILES216 = 0, 1, 2
 GENERATORS = {"random": GEN_RANDOM, "repetitive": GEN_REPETITIVE, "tiles216": GEN_TILES216}
@@ -46,7 +47,8 @@ EXPORTS = ("lz4mi_status_message", "lz4mi_init", "lz4mi_device_count", "lz4mi_ve
            "lz4mi_build_id", "lz4mi_xxh32_reset", "lz4mi_xxh32_update", "lz4mi_xxh32_digest",
            "lz4mi_frame_decompress", "lz4mi_frame_index", "lz4mi_compress_chain",
            "lz4mi_host_compress_block", "lz4mi_host_compress_chain", "lz4mi_host_decompress_block",
-           "lz4mi_decoded_sizes", "lz4mi_host_decoded_size", "lz4mi_host_block_read_end")
+           "lz4mi_decoded_sizes", "lz4mi_host_decoded_size", "lz4mi_host_block_read_end",
+           "lz4mi_verify_blocks", "lz4mi_host_verify_blocks")
 
 
 class Lz4miError(RuntimeError):
@@ -119,6 +121,10 @@ def lib():
         L.lz4mi_host_decoded_size.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _vp]
         L.lz4mi_host_block_read_end.restype = ctypes.c_int64
         L.lz4mi_host_block_read_end.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64]
+        L.lz4mi_verify_blocks.restype = ctypes.c_int32
+        L.lz4mi_verify_blocks.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp]
+        L.lz4mi_host_verify_blocks.restype = ctypes.c_int32
+        L.lz4mi_host_verify_blocks.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32]
         L.lz4mi_frame_index.restype = ctypes.c_int32
         L.lz4mi_frame_index.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp]
         L.lz4mi_generate_blocks.restype = ctypes.c_int32
@@ -423,6 +429,36 @@ def xxh32_blocks(blocks, seed=0, standard=False):
     return h
 
 
+def _records(buf, offs, lens_or_words):
+    a = _u8(buf)
+    off = np.ascontiguousarray(offs, dtype=np.uint64)
+    ln = np.ascontiguousarray(np.asarray(lens_or_words, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    assert off.ndim == 1 and off.shape == ln.shape
+    # (an empty buffer still needs an address: the call refuses NULL inputs)
+    return a if a.size else np.zeros(1, dtype=np.uint8), a.size, off, ln
+
+
+def verify_blocks(buf, offs, lens_or_words, frame_words=False):
+    """Frame block checksums checked on the GPU (lz4mi_verify_blocks, host pointers): record b is the
+    payload buf[offs[b] : offs[b] + n] and the LE32 behind it; -> int32 statuses, 0 or
+    ERR_BLOCK_CHECKSUM (a record that buf's end cuts included). frame_words: the lengths are frame
+    size words (bit 31 = stored, masked off)."""
+    a, total, off, ln = _records(buf, offs, lens_or_words)
+    status = np.zeros(off.size, dtype=np.int32)
+    _check(lib().lz4mi_verify_blocks(_p(a), total, _p(off), _p(ln), status.ctypes.data, off.size,
+                                     FRAME_WORDS if frame_words else 0, None))
+    return status
+
+
+def host_verify_blocks(buf, offs, lens_or_words, frame_words=False):
+    """verify_blocks on the calling thread (lz4mi_host_verify_blocks, no device needed)."""
+    a, total, off, ln = _records(buf, offs, lens_or_words)
+    status = np.zeros(off.size, dtype=np.int32)
+    _check(lib().lz4mi_host_verify_blocks(_p(a), total, _p(off), _p(ln), status.ctypes.data, off.size,
+                                          FRAME_WORDS if frame_words else 0))
+    return status
+
+
 # -------------------------------------------------------------- device API
 # Raw device pointers (ints, e.g. torch tensor .data_ptr()) and a hipStream_t
 # handle (int, e.g. torch.cuda.current_stream().cuda_stream). Async.
@@ -447,6 +483,14 @@ def decoded_sizes_dev(in_ptr, in_off_ptr, in_len_ptr, out_len_ptr, status_ptr, n
                                      DEVICE_PTRS | (FRAME_WORDS if frame_words else 0), stream or None))
 
 
+def verify_blocks_dev(in_ptr, in_total, in_off_ptr, in_len_ptr, status_ptr, nblocks, stream=0, frame_words=False):
+    """Block checksums of a batch on device pointers (lz4mi_verify_blocks): asynchronous on `stream`,
+    nothing read back; status 0 or ERR_BLOCK_CHECKSUM per record. in_total: the size of the buffer at
+    in_ptr (nothing past it is read). frame_words: in_len holds frame size words."""
+    _check(lib().lz4mi_verify_blocks(in_ptr, in_total, in_off_ptr, in_len_ptr, status_ptr, nblocks,
+                                     DEVICE_PTRS | (FRAME_WORDS if frame_words else 0), stream or None))
+
+
 def compress_blocks_dev(in_ptr, in_off_ptr, in_len_ptr, out_ptr, out_off_ptr, out_len_ptr, nblocks, stream=0):
     _check(lib().lz4mi_compress_blocks(in_ptr, in_off_ptr, in_len_ptr, out_ptr, out_off_ptr, out_len_ptr, nblocks,
                                        DEVICE_PTRS, stream or None))
@@ -457,15 +501,18 @@ def xxh32_blocks_dev(in_ptr, off_ptr, len_ptr, hashes_ptr, nblocks, seed=0, stre
                                     DEVICE_PTRS | (XXH_STANDARD if standard else 0), stream or None))
 
 
-def frame_decompress_dev(frame_ptr, frame_len, out_ptr, out_cap, stream=0, js_exact=False, linked=False):
+def frame_decompress_dev(frame_ptr, frame_len, out_ptr, out_cap, stream=0, js_exact=False, linked=False,
+                         verify_blocks=False):
     """Decode a device-resident LZ4 frame into out (device pointers): returns the info dict
     (include/lz4mi.h lz4mi_frame_decompress); raises if the frame needs the host path.
     linked: the compressed blocks go in one linked call (LZ4MI_LINKED, not with js_exact; "exact":
-    LZ4MI_LINKED_EXACT, that call in the reference decoder's bytes)."""
+    LZ4MI_LINKED_EXACT, that call in the reference decoder's bytes). verify_blocks: block checksums
+    (FLG 0x10) are checked on the device (LZ4MI_VERIFY_BLOCKS): a mismatch is status
+    ERR_BLOCK_CHECKSUM with written 0."""
     info = np.zeros(8, dtype=np.int64)
     _check(lib().lz4mi_frame_decompress(frame_ptr, frame_len, out_ptr, out_cap, info.ctypes.data,
-                                        DEVICE_PTRS | (JS_EXACT if js_exact else 0) | _linked_flag(linked),
-                                        stream or None))
+                                        DEVICE_PTRS | (JS_EXACT if js_exact else 0) | _linked_flag(linked) |
+                                        (VERIFY_BLOCKS if verify_blocks else 0), stream or None))
     keys = ("status", "flg", "content_size", "written", "stored_blocks", "checksum_pos", "block_max", "overflow")
     return dict(zip(keys, (int(x) for x in info)))
 

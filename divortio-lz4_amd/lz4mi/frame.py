@@ -648,9 +648,32 @@ class DeviceDecoder:
         res = torch.cat([out[b * block_max:b * block_max + ll[b]] for b in range(nb)])
         return res, status
 
+    def verify(self, rng, pay_rel, word):
+        """The block checksums (FLG 0x10) of this rank's run, in one launch (lz4mi_verify_blocks,
+        LZ4MI_FRAME_WORDS): rng ends behind the last block's checksum. Returns the int32 status tensor,
+        0 or ERR_BLOCK_CHECKSUM per block."""
+        import torch
+        import lz4mi
+        if rng.device.type != "cuda":
+            rng = rng.to("cuda")
+            pay_rel, word = pay_rel.to("cuda"), word.to("cuda")
+        dev = rng.device
+        nb = pay_rel.numel()
+        s = self.stream if self.stream is not None else torch.cuda.current_stream(dev)
+        status = torch.zeros(nb, dtype=torch.int32, device=dev)
+        if nb:
+            w32 = torch.where(word >= 2 ** 31, word - 2 ** 32, word).to(torch.int32).contiguous()
+            in_off = pay_rel.contiguous()
+            s.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(s):
+                lz4mi.verify_blocks_dev(rng.data_ptr(), rng.numel(), in_off.data_ptr(), w32.data_ptr(),
+                                        status.data_ptr(), nb, s.cuda_stream, frame_words=True)
+            s.synchronize()
+        return status
+
 
 def decompress_frame_sharded(frame, verify_checksum=True, group=None, root=0, decoder=None, gather=True,
-                             timings=None, device=None, zero_copy=False):
+                             timings=None, device=None, zero_copy=False, verify_blocks=False):
     """Decode an independent-block frame with its blocks shared out over the ranks.
 
     frame: the whole frame on root (1-D uint8 tensor; a CUDA tensor is indexed and scattered
@@ -669,7 +692,10 @@ def decompress_frame_sharded(frame, verify_checksum=True, group=None, root=0, de
     `device`: where this rank's tensors live (default: frame's device on root, else the
     backend's: CUDA for nccl, host for gloo). With a caller's `decoder` the un-gathered result
     is a copy unless `zero_copy`: then it is a view of that decoder's workspace, overwritten
-    by the decoder's next call of the same shape (bench.py keeps one decoder and opts in)."""
+    by the decoder's next call of the same shape (bench.py keeps one decoder and opts in).
+    verify_blocks: on a frame with block checksums (FLG 0x10) each rank checks its own run's
+    (decoder.verify; a `decoder` without that method: ValueError) before it decodes; a mismatch on
+    any rank raises ERR_BLOCK_CHECKSUM on every rank, before any block's own error is looked at."""
     import time
     import torch
     import lz4mi
@@ -687,6 +713,8 @@ def decompress_frame_sharded(frame, verify_checksum=True, group=None, root=0, de
         dev = torch.device("cuda", torch.cuda.current_device()) if nccl else torch.device("cpu")
     own_decoder = decoder is None
     decoder = decoder or DeviceDecoder()
+    if verify_blocks and not hasattr(decoder, "verify"):
+        raise ValueError("lz4mi: verify_blocks needs a decoder with a verify(rng, pay_rel, word) method")
     src = dist.get_global_rank(group, root) if (multi and group is not None) else root
     t0 = time.perf_counter()
     # ---- index on root, broadcast (a malformed frame raises on every rank, not only on root)
@@ -758,6 +786,13 @@ def decompress_frame_sharded(frame, verify_checksum=True, group=None, root=0, de
     # each block decodes into block_max bytes (a block's output position depends on the sizes
     # before it, which only the decode gives); the content size is checked on the sum below
     last_cap = bmax
+    if verify_blocks and flg & 0x10:
+        vst = decoder.verify(rng, pay[lo:hi] - a, word[lo:hi])
+        vbad = torch.tensor([int(bool((vst != 0).any()))], dtype=torch.int64, device=dev)
+        if multi:
+            dist.all_reduce(vbad, op=dist.ReduceOp.MAX, group=group)
+        if int(vbad.item()):
+            raise lz4mi.Lz4miError(lz4mi.ERR_BLOCK_CHECKSUM)
     out, status = decoder.decode(rng, pay[lo:hi] - a, word[lo:hi], bmax, last_cap)
     if timings is not None and getattr(decoder, "last_kernel_s", None) is not None:
         timings["kernel_device"] = timings.get("kernel_device", 0.0) + decoder.last_kernel_s
@@ -838,14 +873,17 @@ def content_size_bound(frame_len):
     return 255 * int(frame_len) + 4194304
 
 
-def _decode_measured(frame, head, js_exact, s, linked=False):
+def _decode_measured(frame, head, js_exact, s, linked=False, verify_blocks=False):
     """The measured route of decompress_frame_device: index the frame's blocks on the device,
     measure every block's decoded size in one launch (lz4mi_decoded_sizes), lay the output out
     at the exact positions (exclusive prefix sum on the device) and decode all blocks in one
     batch. Returns (output, position of the content checksum), or None when the frame has to
     go to the host path so that its first error and message stay what they were.
     linked (the "linked" route, spec mode): the batch is one LZ4MI_LINKED call, so the blocks may
-    depend on each other (a block's size does not depend on the bytes before it)."""
+    depend on each other (a block's size does not depend on the bytes before it).
+    verify_blocks: on a frame with block checksums (FLG 0x10) they are checked in one launch over the
+    same index (lz4mi_verify_blocks), read with the size pass's statuses; a mismatch raises
+    ERR_BLOCK_CHECKSUM here (the host route would only hash the frame again)."""
     import torch
     import lz4mi
     dev = frame.device
@@ -880,10 +918,18 @@ def _decode_measured(frame, head, js_exact, s, linked=False):
         mst = torch.empty(nb, dtype=torch.int32, device=dev)
         lz4mi.decoded_sizes_dev(frame.data_ptr(), pay.data_ptr(), word.data_ptr(), sizes.data_ptr(), mst.data_ptr(),
                                 nb, s.cuda_stream, frame_words=True)
+        sums = verify_blocks and int(h[1]) & 0x10
+        if sums:
+            vst = torch.empty(nb, dtype=torch.int32, device=dev)
+            lz4mi.verify_blocks_dev(frame.data_ptr(), n, pay.data_ptr(), word.data_ptr(), vst.data_ptr(), nb,
+                                    s.cuda_stream, frame_words=True)
         sz64 = sizes.to(torch.int64)
         ends = torch.cumsum(sz64, 0)
         comp_max = torch.where(word >= 0, sz64, torch.zeros_like(sz64)).max()   # stored blocks: bit 31 (negative)
-        bad, comp_max, total = torch.stack([(mst != 0).any().to(torch.int64), comp_max, ends[-1]]).cpu().tolist()
+        facts = [(mst != 0).any().to(torch.int64), comp_max, ends[-1]] + ([(vst != 0).any().to(torch.int64)] if sums else [])
+        bad, comp_max, total, *vbad = torch.stack(facts).cpu().tolist()
+        if vbad and vbad[0]:
+            raise lz4mi.Lz4miError(lz4mi.ERR_BLOCK_CHECKSUM)
         # the host path reports these frames' errors: a block the walk fails, a compressed block that
         # decodes to more than the window path's block_max slot, a total other than the content size
         if bad or (size <= 0 and comp_max > bmax) or (size > 0 and total != size):
@@ -913,7 +959,8 @@ def _decode_measured(frame, head, js_exact, s, linked=False):
     return out[:total], int(h[5])
 
 
-def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=None, report=None, linked=False):
+def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=None, report=None, linked=False,
+                            verify_blocks=False):
     """Decode a device-resident frame (1-D uint8 CUDA tensor) on its GPU. Three routes, in this
     order; `report` (a dict, optional) receives {"route": "layout" | "measured" | "host"}
     (with `linked`: "layout" | "linked" | "host"):
@@ -935,6 +982,9 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
     linked="exact" (with or without js_exact): the reference decoder's bytes with the layout route
     passing LZ4MI_LINKED_EXACT, one linked call for a dependent frame with a content size; a frame
     the layout walk declines takes the routes js_exact=True has without `linked`.
+    verify_blocks: on a frame with block checksums (FLG 0x10) every route checks them before a block's
+    own error is looked at -- layout: LZ4MI_VERIFY_BLOCKS; measured / linked: one lz4mi_verify_blocks
+    launch over the block index; host: on the host -- and a mismatch raises ERR_BLOCK_CHECKSUM.
     The content checksum (FLG 0x04) is verified on the host, streamed piece by piece. Returns
     the content as a uint8 CUDA tensor: with a content size that many bytes, zeros behind what
     the blocks wrote (the reference's zero-initialised result). Raises lz4mi.Lz4miError with the
@@ -965,7 +1015,8 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
         # checked before the header's claim sizes any allocation: the host route refuses the frame
         # (ERR_RANGE; the reference's own failure there is the RangeError of new Uint8Array)
         report["route"] = "host"
-        decompress_frame_host(frame.cpu().numpy(), js_exact=js_exact, verify_checksum=verify_checksum)
+        decompress_frame_host(frame.cpu().numpy(), js_exact=js_exact, verify_checksum=verify_checksum,
+                              verify_blocks=verify_blocks)
         raise lz4mi.Lz4miError(lz4mi.ERR_RANGE)
     lk = bool(linked) and not js_exact
     try:
@@ -973,19 +1024,22 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
             raise lz4mi.Lz4miError(lz4mi.ERR_ARG)   # the size field itself is cut: the host route's frame
         out = torch.empty(max(1, size), dtype=torch.uint8, device=frame.device)
         info = lz4mi.frame_decompress_dev(frame.data_ptr(), frame.numel(), out.data_ptr(), size, s.cuda_stream,
-                                          js_exact=js_exact and not lx, linked="exact" if lx else lk)
+                                          js_exact=js_exact and not lx, linked="exact" if lx else lk,
+                                          verify_blocks=verify_blocks)
     except lz4mi.Lz4miError as e:
         if e.status != lz4mi.ERR_ARG:
             raise
         out = None
         got = None
+        report["route"] = "linked" if lk else "measured"   # (also what a block-checksum error there reports)
         if lk:
-            got = _decode_measured(frame, head, False, s, linked=True)
+            got = _decode_measured(frame, head, False, s, linked=True, verify_blocks=verify_blocks)
         elif head.size > 4 and head[4] & 0x20 and not (js_exact and size == 0):
-            got = _decode_measured(frame, head, js_exact, s)
+            got = _decode_measured(frame, head, js_exact, s, verify_blocks=verify_blocks)
         if got is None:
             report["route"] = "host"
-            host = decompress_frame_host(frame.cpu().numpy(), js_exact=js_exact, verify_checksum=verify_checksum)
+            host = decompress_frame_host(frame.cpu().numpy(), js_exact=js_exact, verify_checksum=verify_checksum,
+                                         verify_blocks=verify_blocks)
             return torch.from_numpy(host).to(frame.device)
         report["route"] = "linked" if lk else "measured"
         res, pos = got
@@ -1008,7 +1062,7 @@ def decompress_frame_device(frame, js_exact=False, verify_checksum=True, stream=
     return out
 
 
-def decompress_frame_host(frame, js_exact=False, verify_checksum=True):
+def decompress_frame_host(frame, js_exact=False, verify_checksum=True, verify_blocks=False):
     """A frame in host memory decoded block by block through the host-buffer C-ABI path,
     with the reference's two layouts (bufferDecompress.js:97-186): with a content size every
     block is decoded straight into the result at its position (back-references into earlier
@@ -1021,7 +1075,11 @@ def decompress_frame_host(frame, js_exact=False, verify_checksum=True):
     reference does (decompressBlock gets the size word, bytes past the array read as 0): on the
     host decoder (lz4mi_host_decompress_block over the whole frame), so nothing of the declared
     size is allocated. So is a block whose last offset or length field reaches behind its own end
-    (a size word that is off by a few bytes): the reference reads the frame's bytes there."""
+    (a size word that is off by a few bytes): the reference reads the frame's bytes there.
+
+    verify_blocks: on a frame with block checksums (FLG 0x10) every record is checked on the host
+    (lz4mi_host_verify_blocks) before the first block is decoded; a mismatch, or a record the frame's
+    end cuts, raises ERR_BLOCK_CHECKSUM -- no device is touched."""
     import lz4mi
     f = np.ascontiguousarray(frame, dtype=np.uint8)
     try:
@@ -1033,6 +1091,9 @@ def decompress_frame_host(frame, js_exact=False, verify_checksum=True):
     size = info["content_size"]
     if size > content_size_bound(f.size):
         raise lz4mi.Lz4miError(lz4mi.ERR_RANGE)
+    if verify_blocks and info["flg"] & 0x10 and blocks:
+        if lz4mi.host_verify_blocks(f, [p for p, _, _ in blocks], [n for _, n, _ in blocks]).any():
+            raise lz4mi.Lz4miError(lz4mi.ERR_BLOCK_CHECKSUM)
 
     def block(p, n, out, pos, window=None):
         """decompressBlock(data, p, n, out, pos, window): bytes written."""

@@ -80,6 +80,9 @@ extern "C" {
                                     of the reference decoder run on the blocks in order on one array, its
                                     double-copy-tail rewrite (F1) across block boundaries included. Implies
                                     LZ4MI_LINKED. Contract: lz4mi_decompress_blocks. */
+#define LZ4MI_VERIFY_BLOCKS 0x200u /* lz4mi_frame_decompress: check the frame's block checksums (FLG 0x10) on the
+                                    device, lz4mi_verify_blocks over the frame's payloads; a mismatch is the
+                                    frame's error LZ4MI_ERR_BLOCK_CHECKSUM. No effect on a frame without them. */
 
 /* Largest block the kernels accept (the reference's largest block size is 4 MiB;
  * raw calls may pass more, up to 2^31-1 like the reference's `|0` arithmetic). */
@@ -259,6 +262,30 @@ int32_t lz4mi_xxh32_blocks(const uint8_t* in, const uint64_t* off, const uint32_
                            uint32_t* hashes, uint32_t nblocks, uint32_t flags, void* stream);
 
 /*
+ * Batched check of frame BLOCK CHECKSUMS on the GPU, in place.
+ * Replaces nothing in the reference, whose reader skips them (src/buffer/bufferDecompress.js:191); it is the
+ * check LZ4.decompress(..., verifyBlockChecksum) of the JS layer makes, without reading a hash back.
+ * Record b is the payload in[in_off[b] .. +n) and the LE32 behind it, n = in_len[b]; status[b] = LZ4MI_OK when
+ * that word equals XXH32 (spec convergence, seed 0) of the payload, else LZ4MI_ERR_BLOCK_CHECKSUM. in_total is
+ * the size of `in`: nothing outside in[0 .. in_total) is read, and a record the end cuts (in_off[b] + n + 4 >
+ * in_total) is LZ4MI_ERR_BLOCK_CHECKSUM without being hashed, as the JS layer reports it.
+ * flags: LZ4MI_DEVICE_PTRS (asynchronous on `stream`, no scratch, nothing read back); LZ4MI_FRAME_WORDS
+ * (in_len[b] is a frame size word: n = word & 0x7FFFFFFF; a stored block's payload is its raw bytes and is
+ * hashed like any other). Any other flag: LZ4MI_ERR_ARG, as are a NULL status and NULL inputs with
+ * nblocks > 0 (both before the device is looked at). With host pointers each whole record (payload + 4 bytes)
+ * is staged, the kernel run and status[] copied back. One quad of lanes per record, as lz4mi_xxh32_blocks.
+ * Footprint: only status[0 .. nblocks) is written.
+ */
+int32_t lz4mi_verify_blocks(const uint8_t* in, uint64_t in_total, const uint64_t* in_off, const uint32_t* in_len,
+                            int32_t* status, uint32_t nblocks, uint32_t flags, void* stream);
+/*
+ * The same contract on the calling thread (host pointers, no device needed; flags: LZ4MI_FRAME_WORDS only):
+ * the checker of the GPU pass, and what the host frame route uses.
+ */
+int32_t lz4mi_host_verify_blocks(const uint8_t* in, uint64_t in_total, const uint64_t* in_off, const uint32_t* in_len,
+                                 int32_t* status, uint32_t nblocks, uint32_t flags);
+
+/*
  * Frame block records on the device (independent-block frames).
  * Replaces the record writing of compressBuffer's block loop, src/buffer/bufferCompress.js:209-239:
  * block b's record goes to frame[rec_off[b] ..): LE32 comp_len[b] and the compressed bytes
@@ -293,6 +320,14 @@ int32_t lz4mi_frame_pack(const uint8_t* raw, const uint64_t* raw_off, const uint
  * | LZ4MI_LINKED_EXACT (not with LZ4MI_JS_EXACT: LZ4MI_ERR_ARG): the same in the reference decoder's
  * bytes; a block the linked call refuses (the one after a stored block, usually) is decoded alone in
  * reference mode and the blocks after it go into a new linked call.
+ * | LZ4MI_VERIFY_BLOCKS (with any of the above): on a frame with block checksums (FLG 0x10) the payloads of
+ * both block lists are checked on the same stream (lz4mi_verify_blocks), the statuses read back with the
+ * lists. Header errors and the frames this path does not take come first, as without the flag; then any
+ * failing block checksum gives info[0] = LZ4MI_ERR_BLOCK_CHECKSUM, info[3] = 0 and LZ4MI_OK -- before the
+ * layout checks on the decoded lengths (a damaged payload would fail them as LZ4MI_ERR_ARG) and before
+ * every block's own error, a stored block's LZ4MI_ERR_RANGE included: all checksums are checked before a
+ * block's result is looked at, the JS layer's rule. The decode launches may have run by then: the bytes of
+ * out[0 .. content size) are unspecified, nothing outside them is written. Without FLG 0x10: no effect.
  * Synchronous (reads the header and the block lists back). Returns LZ4MI_ERR_ARG for frames
  * this path does not take (no content size, a block layout other than the reference encoder's,
  * out_cap too small): decode those with the host-buffer path block by block.
