@@ -60,6 +60,7 @@ struct StreamCtx {
     Scratch scan;         // frame_decompress: block lists of the device frame walk
     Scratch order;        // batch decode: the blocks' dispatch order (lz4mi_block_order_kernel)
     Scratch small;        // small-batch decode: exported sequences and output pointers (lz4mi_expand.hip)
+    Scratch frames;       // frame batches: the size pass's words and results; the decode's per-block arrays
 };
 
 struct Ctx {
@@ -196,8 +197,10 @@ extern "C" __attribute__((visibility("hidden"))) void lz4mi_advise_output(void* 
 
 namespace {
 
+// isolate: -1 = a batch's blocks are isolated, a lone block reads what precedes it (lz4mi_decompress_blocks);
+// 1 = always (lz4mi_frames_decompress: a frame's lone block may not read the caller's bytes below its slot)
 hipError_t decode_launch(const Batch& b, int mode, hipStream_t s, Scratch* order, Scratch* small = nullptr,
-                         uint32_t in_max = 0, uint32_t out_max = 0) {
+                         uint32_t in_max = 0, uint32_t out_max = 0, int isolate = -1) {
     const uint32_t nblocks = b.nblocks;
     if (small && (mode == 0 || mode == 2) && nblocks <= small_blocks()) {
         const XLimits x = export_limits(in_max, out_max);
@@ -214,7 +217,7 @@ hipError_t decode_launch(const Batch& b, int mode, hipStream_t s, Scratch* order
         if (order->ensure((size_t)nblocks * 4, s) == hipSuccess) ord = order->as<uint32_t>();
         else (void)hipGetLastError();   // index order instead
     }
-    return lz4mi_launch_decompress(b, mode, ord, s);
+    return lz4mi_launch_decompress(b, mode, isolate < 0 ? (nblocks > 1 ? 1 : 0) : isolate, ord, s);
 }
 
 // LZ4MI_LINKED (include/lz4mi.h; kernels: lz4mi_expand.hip "linked mode"): the batch is cut into
@@ -269,7 +272,7 @@ hipError_t linked_launch(const Batch& b, int fw, int f1, hipStream_t s, Scratch*
     g_linked_stats[3] = xo;
     if (!wmax) {
         for (uint32_t k = 0; k < nblocks; ++k) {
-            e = lz4mi_launch_decompress(b.slice(k, 1), (fw ? 4 : 0) | (f1 ? 2 : 0), nullptr, s);
+            e = lz4mi_launch_decompress(b.slice(k, 1), (fw ? 4 : 0) | (f1 ? 2 : 0), 0, nullptr, s);
             if (e != hipSuccess) return e;
         }
         return lz4mi_launch_linked_fail(b.out_len, b.status, nblocks, small->as<uint32_t>(), s);
@@ -1056,6 +1059,69 @@ int32_t lz4mi_frame_index(const uint8_t* frame, uint64_t len, uint64_t* pay_off,
     if (!(flags & LZ4MI_DEVICE_PTRS) || !frame || !info || (cap_blocks && (!pay_off || !size_word)))
         return LZ4MI_ERR_ARG;
     LZ4MI_TRY(lz4mi_launch_frame_index(frame, len, cap_blocks, pay_off, size_word, info, pick_stream(stream)));
+    return LZ4MI_OK;
+}
+
+// A batch of frames (include/lz4mi.h; the passes: lz4mi_frames.hip). Both calls only enqueue.
+int32_t lz4mi_frames_index(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len, uint32_t nframes,
+                           uint64_t* blk_in_off, uint32_t* blk_word, uint32_t* blk_frame, uint32_t* blk_size,
+                           uint32_t cap_blocks, int64_t* finfo, int64_t* totals, uint32_t flags, void* stream) {
+    if (!(flags & LZ4MI_DEVICE_PTRS) || (flags & ~(LZ4MI_DEVICE_PTRS | LZ4MI_FRAMES_MEASURE | LZ4MI_JS_EXACT)))
+        return LZ4MI_ERR_ARG;
+    if (!finfo || !totals || (nframes && (!in || !frame_off || !frame_len)) ||
+        (cap_blocks && (!blk_in_off || !blk_word || !blk_frame || !blk_size)))
+        return LZ4MI_ERR_ARG;
+    DeviceGuard dg;
+    if (dg.status()) return dg.status();
+    hipStream_t s = pick_stream(stream);
+    StreamCtx* c = stream_ctx(s);
+    std::lock_guard<std::mutex> sl(c->mu);
+    // the size pass's input words (0 = not measured) and its results, per listed block
+    LZ4MI_TRY(c->frames.ensure(12ull * cap_blocks + 64, s));
+    uint32_t* meas_word = c->frames.as<uint32_t>();
+    uint32_t* msize = meas_word + cap_blocks;
+    int32_t* mstatus = (int32_t*)(msize + cap_blocks);
+    LZ4MI_TRY(lz4mi_launch_frames_index(in, frame_off, frame_len, nframes, blk_in_off, blk_word, blk_frame, blk_size,
+                                        cap_blocks, finfo, totals, meas_word, msize, mstatus, flags, s));
+    return LZ4MI_OK;
+}
+
+int32_t lz4mi_frames_decompress(const uint8_t* in, const uint64_t* blk_in_off, const uint32_t* blk_word,
+                                const uint32_t* blk_frame, const uint32_t* blk_size, uint32_t nblocks, int64_t* finfo,
+                                uint32_t nframes, uint8_t* out, const uint64_t* frame_out_off,
+                                const uint64_t* frame_out_cap, uint32_t flags, void* stream) {
+    if (!(flags & LZ4MI_DEVICE_PTRS) || (flags & ~(LZ4MI_DEVICE_PTRS | LZ4MI_JS_EXACT | LZ4MI_VERIFY_CONTENT)))
+        return LZ4MI_ERR_ARG;
+    if ((nframes && (!finfo || !frame_out_off || !frame_out_cap || !out || !in)) ||
+        (nblocks && (!blk_in_off || !blk_word || !blk_frame || !blk_size)))
+        return LZ4MI_ERR_ARG;
+    DeviceGuard dg;
+    if (dg.status()) return dg.status();
+    if (nframes == 0) return LZ4MI_OK;
+    hipStream_t s = pick_stream(stream);
+    StreamCtx* c = stream_ctx(s);
+    std::lock_guard<std::mutex> sl(c->mu);
+    // per block: out_off (u64), then word, out_cap, out_len, status; per frame: the hash list (offset u64, then
+    // length, hashed, digest). The first three are zeroed: a block no decoded frame claims is a no-op.
+    const size_t nb = nblocks, nf = nframes, nb2 = (nb + 1) & ~(size_t)1;
+    LZ4MI_TRY(c->frames.ensure(8 * nb + 4 * 4 * nb2 + 8 * nf + 3 * 4 * nf + 64, s));
+    uint64_t* out_off = c->frames.as<uint64_t>();
+    uint32_t* word = (uint32_t*)(out_off + nb);
+    uint32_t* out_cap = word + nb2;
+    uint32_t* out_len = out_cap + nb2;
+    int32_t* status = (int32_t*)(out_len + nb2);
+    uint64_t* hash_off = (uint64_t*)(status + nb2);
+    uint32_t* hash_len = (uint32_t*)(hash_off + nf);
+    uint32_t* hashed = hash_len + nf;
+    uint32_t* digest = hashed + nf;
+    if (nb) LZ4MI_TRY(hipMemsetAsync(out_off, 0, 8 * nb + 2 * 4 * nb2, s));
+    LZ4MI_TRY(lz4mi_launch_frames_place(finfo, nframes, blk_word, blk_size, nblocks, frame_out_off, frame_out_cap, word,
+                                        out_off, out_cap, flags, s));
+    // the batch kernel (never the small path), frame words, every block isolated -- a lone block too
+    const Batch batch{in, blk_in_off, word, out, out_off, out_cap, nullptr, 0, out_len, status, nblocks};
+    LZ4MI_TRY(decode_launch(batch, ((flags & LZ4MI_JS_EXACT) ? 2 : 0) | 4, s, &c->order, nullptr, 0, 0, 1));
+    LZ4MI_TRY(lz4mi_launch_frames_finish(finfo, nframes, nblocks, word, out_off, out_cap, out_len, status, out,
+                                         frame_out_off, hash_off, hash_len, hashed, digest, flags, s));
     return LZ4MI_OK;
 }
 

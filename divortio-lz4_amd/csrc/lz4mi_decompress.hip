@@ -2312,15 +2312,17 @@ static DecArgs dec_args(const Batch& b, int isolate, int f1check) {
                    b.nblocks, isolate, f1check};
 }
 
-extern "C" hipError_t lz4mi_launch_decompress(const Batch& b, int mode, uint32_t* order, hipStream_t stream) {
+extern "C" hipError_t lz4mi_launch_decompress(const Batch& b, int mode, int isolate, uint32_t* order,
+                                              hipStream_t stream) {
     // mode 0: LZ4 spec; 1: reference-exact serial kernel; 2: spec kernel with the in-chunk
     // reference-exact fix-up of every chunk a double-copy-tail rewrite changes (f1_fixup).
     // order: nblocks words of scratch for the dispatch order (nullptr: index order)
     // mode bit 2 (4): in_len holds frame size words (LZ4MI_FRAME_WORDS)
+    // isolate: the blocks may not read below their own start (a batch; a lone block of a frame batch)
     const int fw = (mode & 4) ? 1 : 0;
     mode &= 3;
     const uint32_t nblocks = b.nblocks;
-    DecArgs a = dec_args(b, nblocks > 1 ? 1 : 0, mode == 2 ? 1 : 0);
+    DecArgs a = dec_args(b, isolate, mode == 2 ? 1 : 0);
     a.frame_words = fw;
     if (nblocks == 0) return hipSuccess;
     if (mode == 1) return lz4mi_launch_decompress_serial(a, stream);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/lz4mi.h"
+#include "lz4mi_frames.h"
 
 extern "C" __attribute__((visibility("hidden"))) void lz4mi_advise_output(void* p, uint64_t n);   // (lz4mi_capi.cpp)
 
@@ -374,4 +375,49 @@ extern "C" int64_t lz4mi_host_block_read_end(const uint8_t* in, uint64_t in_tota
     int64_t read_end = in_off;
     walk_block(in, in_total, in_off, in_size, &st, &read_end);
     return read_end;
+}
+
+// lz4mi_frames_index on the calling thread (include/lz4mi.h): the same per-frame steps (lz4mi_frames.h) in the
+// device passes' order -- count, exclusive scan, fill, measure, sizes, totals -- with lz4mi_host_decoded_size
+// over each block alone (zeros behind its end, as lz4mi_decoded_sizes reads them) as the measurement.
+extern "C" int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len,
+                                           uint32_t nframes, uint64_t* blk_in_off, uint32_t* blk_word,
+                                           uint32_t* blk_frame, uint32_t* blk_size, uint32_t cap_blocks,
+                                           int64_t* finfo, int64_t* totals, uint32_t flags) {
+    namespace fr = lz4mi::frames;
+    if (flags & ~(LZ4MI_FRAMES_MEASURE | LZ4MI_JS_EXACT)) return LZ4MI_ERR_ARG;
+    if (!finfo || !totals || (nframes && (!in || !frame_off || !frame_len)) ||
+        (cap_blocks && (!blk_in_off || !blk_word || !blk_frame || !blk_size)))
+        return LZ4MI_ERR_ARG;
+    uint64_t need = 0;
+    for (uint32_t f = 0; f < nframes; ++f) {
+        int64_t* fi = finfo + 8ull * f;
+        fr::count_frame(in + frame_off[f], frame_len[f], fi);
+        fi[fr::kFirst] = (int64_t)need;
+        need += fr::listed(fi);
+    }
+    std::vector<uint32_t> meas_word(cap_blocks, 0u), msize(cap_blocks, 0u);
+    std::vector<int32_t> mstatus(cap_blocks, 0);
+    for (uint32_t f = 0; f < nframes; ++f)
+        fr::fill_frame(in + frame_off[f], frame_len[f], frame_off[f], f, finfo + 8ull * f, blk_in_off, blk_word,
+                       blk_frame, meas_word.data(), cap_blocks, flags);
+    for (uint32_t b = 0; b < cap_blocks; ++b) {
+        const uint32_t w = meas_word[b];
+        if (!w) continue;
+        if (w & 0x80000000u) {
+            msize[b] = w & 0x7FFFFFFFu;
+            continue;
+        }
+        msize[b] = (uint32_t)lz4mi_host_decoded_size(in + blk_in_off[b], w, 0, w, &mstatus[b]);
+    }
+    totals[0] = (int64_t)need;
+    totals[1] = totals[2] = totals[3] = 0;
+    for (uint32_t f = 0; f < nframes; ++f) {
+        int64_t* fi = finfo + 8ull * f;
+        fr::size_frame(fi, blk_word, msize.data(), mstatus.data(), blk_size);
+        totals[1] += (int64_t)fr::listed(fi);
+        if (!fi[fr::kErr] && !fi[fr::kDecline]) totals[2] += fi[fr::kTotal];
+        if (fi[fr::kDecline]) ++totals[3];
+    }
+    return LZ4MI_OK;
 }

@@ -76,7 +76,8 @@ inline XLayout x_layout(uint32_t nblocks, uint32_t x_in_max, uint32_t x_out_max,
 extern "C" {
 
 // ---- decoder (lz4mi_decompress.hip, lz4mi_decompress_serial.hip, lz4mi_expand.hip, lz4mi_size.hip)
-hipError_t lz4mi_launch_decompress(const lz4mi::Batch& b, int mode, uint32_t* order, hipStream_t stream);
+// isolate: a back-reference below a block's own start is LZ4MI_ERR_CROSS_BLOCK, not followed
+hipError_t lz4mi_launch_decompress(const lz4mi::Batch& b, int mode, int isolate, uint32_t* order, hipStream_t stream);
 hipError_t lz4mi_launch_decompress_serial(const lz4mi::DecArgs& a, hipStream_t stream);
 size_t lz4mi_small_scratch_bytes(uint32_t nblocks, uint32_t x_in_max, uint32_t x_out_max);
 hipError_t lz4mi_launch_decompress_small(const lz4mi::Batch& b, uint32_t x_in_max, uint32_t x_out_max, void* xs,
@@ -123,5 +124,21 @@ hipError_t lz4mi_launch_frame_pack(const uint8_t* raw, const uint64_t* raw_off, 
                                    uint64_t* sum_off, uint32_t* pay_len, hipStream_t stream);
 hipError_t lz4mi_launch_frame_index(const uint8_t* f, uint64_t len, uint32_t cap_blocks, uint64_t* pay_off,
                                     uint32_t* size_word, int64_t* info, hipStream_t stream);
+
+// ---- frame batches (lz4mi_frames.hip)
+hipError_t lz4mi_launch_frames_index(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len,
+                                     uint32_t nframes, uint64_t* blk_in_off, uint32_t* blk_word, uint32_t* blk_frame,
+                                     uint32_t* blk_size, uint32_t cap_blocks, int64_t* finfo, int64_t* totals,
+                                     uint32_t* meas_word, uint32_t* msize, int32_t* mstatus, uint32_t flags,
+                                     hipStream_t stream);
+hipError_t lz4mi_launch_frames_place(int64_t* finfo, uint32_t nframes, const uint32_t* blk_word,
+                                     const uint32_t* blk_size, uint32_t nblocks, const uint64_t* frame_out_off,
+                                     const uint64_t* frame_out_cap, uint32_t* word, uint64_t* out_off, uint32_t* out_cap,
+                                     uint32_t flags, hipStream_t stream);
+hipError_t lz4mi_launch_frames_finish(int64_t* finfo, uint32_t nframes, uint32_t nblocks, const uint32_t* word,
+                                      const uint64_t* out_off, const uint32_t* out_cap, const uint32_t* out_len,
+                                      const int32_t* status, uint8_t* out, const uint64_t* frame_out_off,
+                                      uint64_t* hash_off, uint32_t* hash_len, uint32_t* hashed, uint32_t* digest,
+                                      uint32_t flags, hipStream_t stream);
 
 }  // extern "C"

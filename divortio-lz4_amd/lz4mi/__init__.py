@@ -33,6 +33,12 @@ FRAME_WORDS = 0x40
 LINKED = 0x80
 LINKED_EXACT = 0x100
 VERIFY_BLOCKS = 0x200
+VERIFY_CONTENT = 0x400
+FRAMES_MEASURE = 0x800
+
+# finfo[f][7] of the frame batch calls (include/lz4mi.h LZ4MI_FRAMES_DECLINE_*)
+(DECLINE_CAP_BLOCKS, DECLINE_PAST_END, DECLINE_EMPTY, DECLINE_UNSIZED_EXACT, DECLINE_MEASURE, DECLINE_SIZE_MISMATCH,
+ DECLINE_OUT_CAP, DECLINE_LAYOUT, DECLINE_DEPENDENT, DECLINE_HASH_4G) = range(1, 11)
 
 GEN_RANDOM, GEN_REPETITIVE, GEN_TILES216 = 0, 1, 2
 GENERATORS = {"random": GEN_RANDOM, "repetitive": GEN_REPETITIVE, "tiles216": GEN_TILES216}
@@ -48,7 +54,8 @@ EXPORTS = ("lz4mi_status_message", "lz4mi_init", "lz4mi_device_count", "lz4mi_ve
            "lz4mi_frame_decompress", "lz4mi_frame_index", "lz4mi_compress_chain",
            "lz4mi_host_compress_block", "lz4mi_host_compress_chain", "lz4mi_host_decompress_block",
            "lz4mi_decoded_sizes", "lz4mi_host_decoded_size", "lz4mi_host_block_read_end",
-           "lz4mi_verify_blocks", "lz4mi_host_verify_blocks")
+           "lz4mi_verify_blocks", "lz4mi_host_verify_blocks", "lz4mi_frames_index", "lz4mi_frames_decompress",
+           "lz4mi_host_frames_index")
 
 
 class Lz4miError(RuntimeError):
@@ -127,6 +134,15 @@ def lib():
         L.lz4mi_host_verify_blocks.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32]
         L.lz4mi_frame_index.restype = ctypes.c_int32
         L.lz4mi_frame_index.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp]
+        L.lz4mi_frames_index.restype = ctypes.c_int32
+        L.lz4mi_frames_index.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp,
+                                         ctypes.c_uint32, _vp]
+        L.lz4mi_frames_decompress.restype = ctypes.c_int32
+        L.lz4mi_frames_decompress.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _vp,
+                                              _vp, ctypes.c_uint32, _vp]
+        L.lz4mi_host_frames_index.restype = ctypes.c_int32
+        L.lz4mi_host_frames_index.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
+                                              _vp, ctypes.c_uint32]
         L.lz4mi_generate_blocks.restype = ctypes.c_int32
         L.lz4mi_generate_blocks.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                             ctypes.c_uint32, _vp]
@@ -459,6 +475,27 @@ def host_verify_blocks(buf, offs, lens_or_words, frame_words=False):
     return status
 
 
+def host_frames_index(arena, frame_off, frame_len, cap_blocks, measure=False, js_exact=False):
+    """lz4mi_frames_index on the calling thread (lz4mi_host_frames_index, no device needed): the frames
+    arena[frame_off[f] : frame_off[f] + frame_len[f]] -> dict with finfo (nframes x 8 int64), totals (4 int64)
+    and the block lists blk_in_off / blk_word / blk_frame / blk_size (cap_blocks entries each, the first
+    totals[1] of them written)."""
+    a = _u8(arena)
+    off = np.ascontiguousarray(frame_off, dtype=np.uint64)
+    ln = np.ascontiguousarray(frame_len, dtype=np.uint64)
+    assert off.ndim == 1 and off.shape == ln.shape
+    n = off.size
+    res = {"finfo": np.zeros((n, 8), dtype=np.int64), "totals": np.zeros(4, dtype=np.int64),
+           "blk_in_off": np.zeros(cap_blocks, dtype=np.uint64), "blk_word": np.zeros(cap_blocks, dtype=np.uint32),
+           "blk_frame": np.zeros(cap_blocks, dtype=np.uint32), "blk_size": np.zeros(cap_blocks, dtype=np.uint32)}
+    _check(lib().lz4mi_host_frames_index(_p(a) if a.size else np.zeros(1, dtype=np.uint8).ctypes.data, _p(off), _p(ln),
+                                         n, _p(res["blk_in_off"]), _p(res["blk_word"]), _p(res["blk_frame"]),
+                                         _p(res["blk_size"]), cap_blocks, res["finfo"].ctypes.data,
+                                         res["totals"].ctypes.data,
+                                         (FRAMES_MEASURE if measure else 0) | (JS_EXACT if js_exact else 0)))
+    return res
+
+
 # -------------------------------------------------------------- device API
 # Raw device pointers (ints, e.g. torch tensor .data_ptr()) and a hipStream_t
 # handle (int, e.g. torch.cuda.current_stream().cuda_stream). Async.
@@ -515,6 +552,29 @@ def frame_decompress_dev(frame_ptr, frame_len, out_ptr, out_cap, stream=0, js_ex
                                         (VERIFY_BLOCKS if verify_blocks else 0), stream or None))
     keys = ("status", "flg", "content_size", "written", "stored_blocks", "checksum_pos", "block_max", "overflow")
     return dict(zip(keys, (int(x) for x in info)))
+
+
+def frames_index_dev(in_ptr, frame_off_ptr, frame_len_ptr, nframes, blk_in_off_ptr, blk_word_ptr, blk_frame_ptr,
+                     blk_size_ptr, cap_blocks, finfo_ptr, totals_ptr, stream=0, measure=False, js_exact=False):
+    """Block index of a batch of device-resident frames (include/lz4mi.h lz4mi_frames_index): device pointers,
+    asynchronous on `stream`, nothing read back. measure: LZ4MI_FRAMES_MEASURE; js_exact: unsized frames are
+    declined."""
+    _check(lib().lz4mi_frames_index(in_ptr, frame_off_ptr, frame_len_ptr, nframes, blk_in_off_ptr, blk_word_ptr,
+                                    blk_frame_ptr, blk_size_ptr, cap_blocks, finfo_ptr, totals_ptr,
+                                    DEVICE_PTRS | (FRAMES_MEASURE if measure else 0) | (JS_EXACT if js_exact else 0),
+                                    stream or None))
+
+
+def frames_decompress_dev(in_ptr, blk_in_off_ptr, blk_word_ptr, blk_frame_ptr, blk_size_ptr, nblocks, finfo_ptr,
+                          nframes, out_ptr, frame_out_off_ptr, frame_out_cap_ptr, stream=0, js_exact=False,
+                          verify_content=False):
+    """Decode the frames lz4mi_frames_index listed, in one call (include/lz4mi.h lz4mi_frames_decompress): device
+    pointers, asynchronous on `stream`; finfo holds each frame's status, bytes written and decline code afterwards.
+    verify_content: LZ4MI_VERIFY_CONTENT, the content checksums on the device."""
+    _check(lib().lz4mi_frames_decompress(in_ptr, blk_in_off_ptr, blk_word_ptr, blk_frame_ptr, blk_size_ptr, nblocks,
+                                         finfo_ptr, nframes, out_ptr, frame_out_off_ptr, frame_out_cap_ptr,
+                                         DEVICE_PTRS | (JS_EXACT if js_exact else 0) |
+                                         (VERIFY_CONTENT if verify_content else 0), stream or None))
 
 
 def generate_blocks_dev(out_ptr, kind, seed0, block_size, nblocks, stream=0):

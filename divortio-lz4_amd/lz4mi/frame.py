@@ -1135,3 +1135,114 @@ def decompress_frame_host(frame, js_exact=False, verify_checksum=True, verify_bl
         if lz4mi.XXHash32(0, len64=True).update(out).digest() != want:
             raise lz4mi.Lz4miError(lz4mi.ERR_CHECKSUM)
     return out
+
+
+def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measure=False, stream=None, report=None,
+                             return_errors=False, offsets=None, lengths=None, cap_blocks=None):
+    """Decode a batch of device-resident frames with one index call, one output allocation and one decode
+    call (lz4mi_frames_index / lz4mi_frames_decompress): the frames' size words are walked in parallel, one
+    lane per frame, the blocks of all frames decoded by one batch launch, and with verify_checksum the
+    content checksums (FLG 0x04) hashed on the device, one chain per frame, all in one launch.
+
+    frames: a list of 1-D uint8 CUDA tensors, or one such tensor holding frame f at
+    frames[offsets[f] : offsets[f] + lengths[f]] (any alignment). The list form concatenates the frames first,
+    a device copy of all input that doubles its memory for the call: frames that already lie in one tensor
+    should be passed with offsets and lengths. measure: LZ4MI_FRAMES_MEASURE, every
+    frame's block sizes are measured (frames with a content size and partial blocks in the middle).
+    Two host synchronisations: finfo and totals read back after the index (a third when cap_blocks -- the
+    guess of _decode_measured, or the caller's -- was too small and the index runs again with the exact
+    need), and finfo after the decode. A frame the batch declines (finfo[f][7], include/lz4mi.h
+    LZ4MI_FRAMES_DECLINE_*: dependent blocks, the empty frame, cut frames, unsized frames with js_exact, ...)
+    or whose content size is above content_size_bound goes through decompress_frame_device alone, so the
+    result is always complete and what that call gives per frame.
+    report (a dict, optional) receives routes (per frame "batch" or that call's route), declined (per frame
+    the decline code) and index_calls. Returns the list of result tensors: for batch frames views of the one
+    allocation, at 16-byte-aligned offsets. The first failing frame raises lz4mi.Lz4miError with
+    .frame_index; with return_errors the error objects stand in the list instead."""
+    import torch
+    import lz4mi
+    if offsets is None:
+        frames = list(frames)
+        lens = [int(t.numel()) for t in frames]
+        offs = [0] * len(lens)
+        for k in range(1, len(lens)):
+            offs[k] = offs[k - 1] + lens[k - 1]
+        dev = frames[0].device if frames else torch.device("cuda", torch.cuda.current_device())
+    else:
+        offs, lens = [int(x) for x in offsets], [int(x) for x in lengths]
+        dev = frames.device
+    nf = len(lens)
+    if report is None:
+        report = {}
+    report.update(routes=[None] * nf, declined=[0] * nf, index_calls=0)
+    if nf == 0:
+        return []
+    lz4mi.init(dev.index if dev.index is not None else torch.cuda.current_device())
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        arena = torch.cat(frames) if offsets is None else frames
+        if arena.numel() == 0:
+            arena = torch.zeros(1, dtype=torch.uint8, device=dev)
+        span = torch.tensor([offs, lens], dtype=torch.int64, device=dev)
+        # the block lists are sized as _decode_measured sizes them: for a compression ratio of 4 at the
+        # smallest block size; the index reports the exact need when that was too small
+        nbytes = sum(lens)
+        cap = cap_blocks if cap_blocks is not None else min(nbytes // 4 + 2, 4 * (nbytes // 65536) + 2 * nf + 64)
+        while True:
+            cap = max(1, int(cap))
+            blk_in_off = torch.empty(cap, dtype=torch.int64, device=dev)
+            blk32 = torch.empty((3, cap), dtype=torch.int32, device=dev)   # word, frame, size
+            fin = torch.zeros(8 * nf + 4, dtype=torch.int64, device=dev)   # finfo, then totals
+            lz4mi.frames_index_dev(arena.data_ptr(), span[0].data_ptr(), span[1].data_ptr(), nf, blk_in_off.data_ptr(),
+                                   blk32[0].data_ptr(), blk32[1].data_ptr(), blk32[2].data_ptr(), cap, fin.data_ptr(),
+                                   fin.data_ptr() + 64 * nf, s.cuda_stream, measure=measure, js_exact=js_exact)
+            report["index_calls"] += 1
+            h = fin.cpu().numpy()
+            need = int(h[8 * nf])
+            if need <= cap or report["index_calls"] > 1:
+                break
+            cap = need
+        info = h[:8 * nf].reshape(nf, 8)
+        listed = int(h[8 * nf + 1])     # the decode launch and its scratch take the blocks listed, not the guess
+        # one allocation, the frames the call decodes at 16-byte-aligned offsets; a content size above the
+        # bound sizes nothing: that frame gets no room, which declines it
+        out_off, out_cap, at = [0] * nf, [0] * nf, 0
+        for f in range(nf):
+            total = int(info[f, 3])
+            size = int(info[f, 2]) & 0xFFFFFFFFFFFFFFFF
+            if info[f, 0] or info[f, 7] or size > content_size_bound(lens[f]):
+                continue
+            out_off[f], out_cap[f] = at, total
+            at += (total + 15) & ~15
+        out = torch.empty(max(1, at), dtype=torch.uint8, device=dev)
+        slots = torch.tensor([out_off, out_cap], dtype=torch.int64, device=dev)
+        lz4mi.frames_decompress_dev(arena.data_ptr(), blk_in_off.data_ptr(), blk32[0].data_ptr(), blk32[1].data_ptr(),
+                                    blk32[2].data_ptr(), listed, fin.data_ptr(), nf, out.data_ptr(), slots[0].data_ptr(),
+                                    slots[1].data_ptr(), s.cuda_stream, js_exact=js_exact,
+                                    verify_content=verify_checksum)
+        done = fin[:8 * nf].cpu().numpy().reshape(nf, 8)
+    res = [None] * nf
+    for f in range(nf):
+        err = None
+        if done[f, 7]:
+            report["declined"][f] = int(done[f, 7])
+            one = arena[offs[f]:offs[f] + lens[f]]
+            r = {}
+            try:
+                res[f] = decompress_frame_device(one, js_exact=js_exact, verify_checksum=verify_checksum, stream=stream,
+                                                 report=r)
+            except lz4mi.Lz4miError as e:
+                err = e
+            report["routes"][f] = r.get("route", "host")
+        else:
+            report["routes"][f] = "batch"
+            if done[f, 0]:
+                err = lz4mi.Lz4miError(int(done[f, 0]))
+            else:
+                res[f] = out[out_off[f]:out_off[f] + out_cap[f]]
+        if err is not None:
+            err.frame_index = f
+            if not return_errors:
+                raise err
+            res[f] = err
+    return res

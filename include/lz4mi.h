@@ -83,6 +83,29 @@ extern "C" {
 #define LZ4MI_VERIFY_BLOCKS 0x200u /* lz4mi_frame_decompress: check the frame's block checksums (FLG 0x10) on the
                                     device, lz4mi_verify_blocks over the frame's payloads; a mismatch is the
                                     frame's error LZ4MI_ERR_BLOCK_CHECKSUM. No effect on a frame without them. */
+#define LZ4MI_VERIFY_CONTENT 0x400u /* lz4mi_frames_decompress: check every decoded frame's content checksum (FLG 0x04)
+                                    on the device, one XXH32 chain (the reference's variant) per frame, all frames
+                                    in one launch; a mismatch is that frame's error LZ4MI_ERR_CHECKSUM. */
+#define LZ4MI_FRAMES_MEASURE 0x800u /* lz4mi_frames_index: measure every frame's block sizes (lz4mi_decoded_sizes),
+                                    also where a content size would give them from the reference encoder's layout:
+                                    for frames with partial blocks in the middle. */
+
+/* ---- why lz4mi_frames_index / lz4mi_frames_decompress leave a frame to the caller (finfo[f][7]) ---- */
+#define LZ4MI_FRAMES_DECLINE_CAP_BLOCKS 1    /* its blocks are not in the lists: cap_blocks (nblocks) too small */
+#define LZ4MI_FRAMES_DECLINE_PAST_END 2      /* the walk of its size words ran past the frame's end (a cut frame) */
+#define LZ4MI_FRAMES_DECLINE_EMPTY 3         /* no blocks, or the content-size flag with size 0 (the empty frame) */
+#define LZ4MI_FRAMES_DECLINE_UNSIZED_EXACT 4 /* no content size, with LZ4MI_JS_EXACT: the reference decodes such a frame
+                                                behind a window, where its tail rewrite lands elsewhere */
+#define LZ4MI_FRAMES_DECLINE_MEASURE 5       /* a measured block fails the size walk, or a frame without a content size
+                                                has a compressed block above its block_max */
+#define LZ4MI_FRAMES_DECLINE_SIZE_MISMATCH 6 /* the measured total differs from the content size */
+#define LZ4MI_FRAMES_DECLINE_OUT_CAP 7       /* the decoded total is above frame_out_cap[f] */
+#define LZ4MI_FRAMES_DECLINE_LAYOUT 8        /* not the reference encoder's layout (a compressed block other than the last
+                                                that does not fill its slot: where lz4mi_frame_decompress returns
+                                                LZ4MI_ERR_ARG); a measured frame with a failing block */
+#define LZ4MI_FRAMES_DECLINE_DEPENDENT 9     /* a block reads the output of the block before it (LZ4MI_ERR_CROSS_BLOCK);
+                                                with LZ4MI_JS_EXACT also block 0's tail rewrite reading below the frame */
+#define LZ4MI_FRAMES_DECLINE_HASH_4G 10      /* LZ4MI_VERIFY_CONTENT and a result of 4 GiB or more */
 
 /* Largest block the kernels accept (the reference's largest block size is 4 MiB;
  * raw calls may pass more, up to 2^31-1 like the reference's `|0` arithmetic). */
@@ -406,6 +429,82 @@ int64_t lz4mi_host_block_read_end(const uint8_t* in, uint64_t in_total, int64_t 
  */
 int32_t lz4mi_frame_index(const uint8_t* frame, uint64_t len, uint64_t* pay_off, uint32_t* size_word,
                           uint32_t cap_blocks, int64_t* info, uint32_t flags, void* stream);
+
+/*
+ * A BATCH OF FRAMES decoded on the device: index, then decompress. Device pointers only (LZ4MI_DEVICE_PTRS
+ * required), asynchronous on `stream`, nothing is read back by either call.
+ * Replaces decompressBuffer (src/buffer/bufferDecompress.js:51-220) called once per frame: frame f is
+ * in[frame_off[f] .. +frame_len[f]) (any alignment; nothing outside these ranges is read). Only the walk inside a
+ * frame is serial, so the frames walk in parallel, one lane each, and the blocks of all of them are decoded by
+ * one LZ4MI_FRAME_WORDS batch launch.
+ *
+ * lz4mi_frames_index lists every frame's blocks in frame order, frame after frame: blk_in_off[b] (absolute in
+ * `in`), blk_word[b] (the raw size word, bit 31 = stored), blk_frame[b], and blk_size[b], the decoded size the
+ * block is given: for a frame with a content size > 0 the reference encoder's layout (a stored block its
+ * declared size; a compressed block min(block_max, content size - position), position advancing by block_max),
+ * for a frame without one -- with LZ4MI_FRAMES_MEASURE for every frame -- the size measured by
+ * lz4mi_decoded_sizes. finfo[f] (8 x int64 per frame):
+ *   [0] the frame's error in the reference's meaning, or 0: after the index call LZ4MI_ERR_MAGIC or
+ *       LZ4MI_ERR_VERSION (checked in this order, before the size field, DictID and HC byte are skipped);
+ *   [1] FLG | BD << 8; bit 16: the frame's sizes were measured; bits 32-63: the LE32 behind the EndMark when FLG
+ *       has 0x04 (the content checksum; bytes the frame's end cuts read as 0). Mask before comparing: FLG is
+ *       [1] & 0xFF, BD is ([1] >> 8) & 0xFF, and the value is negative when the checksum's top bit is set;
+ *   [2] the content size; [3] the decoded total the frame needs in `out` (the content size, or the measured
+ *   sum); [4] its first block in the lists; [5] the position behind the EndMark, relative to the frame;
+ *   [6] its block count; [7] 0 = lz4mi_frames_decompress decodes this frame, else LZ4MI_FRAMES_DECLINE_*.
+ * A declined frame is not an error of the call: the caller decodes it alone (lz4mi_frame_decompress or the
+ * host path). A frame with [0] != 0 or a decline CAP_BLOCKS / PAST_END / EMPTY has no blocks in the lists; the
+ * blocks of the frames that fit are listed without gaps, and a frame whose blocks do not fit cap_blocks lists
+ * none. totals (4 x int64): [0] the blocks needed (call again with that cap_blocks if it is above cap_blocks),
+ * [1] the blocks listed, [2] the sum of [3] over the frames that are neither declined nor in error, [3] the
+ * number of declined frames.
+ * flags: LZ4MI_DEVICE_PTRS | LZ4MI_FRAMES_MEASURE | LZ4MI_JS_EXACT (decides only the UNSIZED_EXACT decline). Any
+ * other flag, a NULL finfo / totals, NULL inputs with nframes > 0 or NULL lists with cap_blocks > 0:
+ * LZ4MI_ERR_ARG before the device is looked at.
+ * Footprint: finfo[0 .. 8 nframes), totals[0 .. 4), and entries [0, totals[1]) of the four lists; nothing else.
+ *
+ * lz4mi_frames_decompress takes the lists and finfo as the index call left them (nblocks = cap_blocks or
+ * totals[1]) and decodes every frame with finfo[f][0] == 0 and finfo[f][7] == 0 into out[frame_out_off[f] ..
+ * +finfo[f][3]), provided that fits frame_out_cap[f]. Afterwards, per frame:
+ *   [0] the reference's error for the frame, as lz4mi_frame_decompress reports it: the first failing block in
+ *       block order (LZ4MI_ERR_* of the block decoder; LZ4MI_ERR_RANGE for a stored block past the content size;
+ *       a back-reference of block 0 below the frame's start is LZ4MI_ERR_DICT_OOB: the frame has no dictionary
+ *       and its result starts at position 0), or LZ4MI_ERR_CHECKSUM (LZ4MI_VERIFY_CONTENT);
+ *   [3] the bytes written: the largest end, relative to the frame's slot and at most its total, of a block with
+ *       status 0 -- lz4mi_frame_decompress's info[3], with one difference: a stored block that fails
+ *       LZ4MI_ERR_RANGE counts nothing here, because it writes nothing (there its bytes are copied clipped at the
+ *       content size and counted up to it);
+ *   [7] may have become OUT_CAP, LAYOUT, DEPENDENT, HASH_4G, UNSIZED_EXACT (LZ4MI_JS_EXACT given to this call
+ *       only: a frame without a content size is declined here as the index call would have) or CAP_BLOCKS (finfo
+ *       does not fit nblocks).
+ * A frame with status 0 and a content size holds content-size bytes, zeros behind what its blocks wrote (the
+ * reference's zero-initialised result). Every block is decoded isolated: no frame reads or writes another
+ * frame's bytes, a lone block included.
+ * flags: LZ4MI_DEVICE_PTRS | LZ4MI_JS_EXACT (the reference decoder's bytes) | LZ4MI_VERIFY_CONTENT. Any other
+ * flag or a NULL required pointer: LZ4MI_ERR_ARG before the device is looked at. LZ4MI_LINKED* and
+ * LZ4MI_VERIFY_BLOCKS are not taken: a linked pass has no barrier at a frame's first slot, and the verify kernel
+ * takes a single in_total; frames with dependent blocks are declined, block checksums are skipped.
+ * Footprint: finfo; of `out`, only bytes inside out[frame_out_off[f] .. +finfo[f][3]) of frames that were
+ * decoded, failed in a block, or were declined as LAYOUT / DEPENDENT (whose bytes there are unspecified). A
+ * frame in error or declined before the decode (every other code) has no byte of `out` written. `in` and the
+ * lists are read only; the per-block scratch lives with the stream.
+ */
+int32_t lz4mi_frames_index(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len, uint32_t nframes,
+                           uint64_t* blk_in_off, uint32_t* blk_word, uint32_t* blk_frame, uint32_t* blk_size,
+                           uint32_t cap_blocks, int64_t* finfo /* nframes x 8 */, int64_t* totals /* 4 */,
+                           uint32_t flags, void* stream);
+int32_t lz4mi_frames_decompress(const uint8_t* in, const uint64_t* blk_in_off, const uint32_t* blk_word,
+                                const uint32_t* blk_frame, const uint32_t* blk_size, uint32_t nblocks,
+                                int64_t* finfo, uint32_t nframes, uint8_t* out, const uint64_t* frame_out_off,
+                                const uint64_t* frame_out_cap, uint32_t flags, void* stream);
+/*
+ * lz4mi_frames_index on the calling thread (host pointers, no device needed; flags: LZ4MI_FRAMES_MEASURE |
+ * LZ4MI_JS_EXACT): the checker of the device passes. Measuring is lz4mi_host_decoded_size over each block alone.
+ */
+int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len,
+                                uint32_t nframes, uint64_t* blk_in_off, uint32_t* blk_word, uint32_t* blk_frame,
+                                uint32_t* blk_size, uint32_t cap_blocks, int64_t* finfo, int64_t* totals,
+                                uint32_t flags);
 
 
 /*
