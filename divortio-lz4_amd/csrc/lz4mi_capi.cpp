@@ -18,6 +18,7 @@
 #include <sys/mman.h>
 
 #include "../../include/lz4mi.h"
+#include "lz4mi_frames_enc.h"
 #include "lz4mi_launch.h"
 
 #ifndef LZ4MI_SRC_HASH
@@ -1122,6 +1123,73 @@ int32_t lz4mi_frames_decompress(const uint8_t* in, const uint64_t* blk_in_off, c
     LZ4MI_TRY(decode_launch(batch, ((flags & LZ4MI_JS_EXACT) ? 2 : 0) | 4, s, &c->order, nullptr, 0, 0, 1));
     LZ4MI_TRY(lz4mi_launch_frames_finish(finfo, nframes, nblocks, word, out_off, out_cap, out_len, status, out,
                                          frame_out_off, hash_off, hash_len, hashed, digest, flags, s));
+    return LZ4MI_OK;
+}
+
+// A batch of buffers into frames (include/lz4mi.h; the passes: lz4mi_frames_enc.hip). Both calls only enqueue.
+uint64_t lz4mi_frame_bound(uint64_t n, uint32_t block_max) {
+    namespace fe = lz4mi::frames_enc;
+    return fe::frame_bound(n, fe::block_bytes(fe::block_id(block_max)));
+}
+
+int32_t lz4mi_frames_plan(const uint64_t* src_off, const uint64_t* src_len, uint32_t nframes, uint32_t block_max,
+                          uint64_t* blk_in_off, uint32_t* blk_len, uint32_t* blk_frame, uint64_t* blk_work_off,
+                          uint32_t cap_blocks, int64_t* finfo, int64_t* totals, uint32_t flags, void* stream) {
+    namespace fe = lz4mi::frames_enc;
+    if (!(flags & LZ4MI_DEVICE_PTRS) || (flags & ~(LZ4MI_DEVICE_PTRS | fe::kFlags))) return LZ4MI_ERR_ARG;
+    if (!finfo || !totals || (nframes && (!src_off || !src_len)) ||
+        (cap_blocks && (!blk_in_off || !blk_len || !blk_frame || !blk_work_off)))
+        return LZ4MI_ERR_ARG;
+    DeviceGuard dg;
+    if (dg.status()) return dg.status();
+    LZ4MI_TRY(lz4mi_launch_frames_plan(src_off, src_len, nframes, fe::block_bytes(fe::block_id(block_max)), blk_in_off,
+                                       blk_len, blk_frame, blk_work_off, cap_blocks, finfo, totals, flags,
+                                       pick_stream(stream)));
+    return LZ4MI_OK;
+}
+
+int32_t lz4mi_frames_compress(const uint8_t* in, const uint64_t* blk_in_off, const uint32_t* blk_len,
+                              const uint32_t* blk_frame, const uint64_t* blk_work_off, uint32_t nblocks, int64_t* finfo,
+                              uint32_t nframes, uint8_t* work, uint64_t work_bytes, uint8_t* out, uint64_t out_total,
+                              const uint64_t* frame_out_off, const uint64_t* frame_out_cap, uint32_t flags,
+                              void* stream) {
+    namespace fe = lz4mi::frames_enc;
+    if (!(flags & LZ4MI_DEVICE_PTRS) || (flags & ~(LZ4MI_DEVICE_PTRS | fe::kFlags))) return LZ4MI_ERR_ARG;
+    if (fe::bad_compress_args(in, blk_in_off, blk_len, blk_frame, blk_work_off, nblocks, finfo, nframes, work, work_bytes,
+                              out, frame_out_off, frame_out_cap, flags))
+        return LZ4MI_ERR_ARG;
+    DeviceGuard dg;
+    if (dg.status()) return dg.status();
+    if (nframes == 0) return LZ4MI_OK;
+    hipStream_t s = pick_stream(stream);
+    StreamCtx* c = stream_ctx(s);
+    std::lock_guard<std::mutex> sl(c->mu);
+    // per block and per frame, in this order: [enc_off, pay_off | hash_off] u64 and [enc_len, pay_len | hash_len]
+    // u32, zeroed; [rec_off, sum_off | hash_dst] u64, set to ~0 (no place); comp_len u32
+    const size_t nb = nblocks, nf = nframes, n64 = 2 * nb + nf, n32 = (n64 + 1) & ~(size_t)1;
+    LZ4MI_TRY(c->frames.ensure(8 * n64 + 4 * n32 + 8 * n64 + 4 * nb + 64, s));
+    uint64_t* enc_off = c->frames.as<uint64_t>();
+    uint64_t* pay_off = enc_off + nb;
+    uint64_t* hash_off = pay_off + nb;
+    uint32_t* enc_len = (uint32_t*)(enc_off + n64);
+    uint32_t* pay_len = enc_len + nb;
+    uint32_t* hash_len = pay_len + nb;
+    uint64_t* rec_off = (uint64_t*)(enc_len + n32);
+    uint64_t* sum_off = rec_off + nb;
+    uint64_t* hash_dst = sum_off + nb;
+    uint32_t* comp_len = (uint32_t*)(rec_off + n64);
+    LZ4MI_TRY(hipMemsetAsync(enc_off, 0, 8 * n64 + 4 * n32, s));
+    LZ4MI_TRY(hipMemsetAsync(rec_off, 0xFF, 8 * n64, s));
+    LZ4MI_TRY(lz4mi_launch_frames_enc_prep(finfo, nframes, nblocks, blk_len, blk_work_off, work_bytes, enc_off, enc_len,
+                                           flags, s));
+    // the batch encoder over the listed blocks, a slice at a time: the table scratch stays at kSlice tables
+    if (nb) LZ4MI_TRY(c->tables.ensure(std::min<size_t>(nb, fe::kSlice) * 16384 * sizeof(int32_t), s));
+    for (uint32_t b0 = 0; b0 < nblocks; b0 += fe::kSlice)
+        LZ4MI_TRY(lz4mi_launch_compress(in, blk_in_off + b0, enc_len + b0, work, enc_off + b0, comp_len + b0,
+                                        std::min(fe::kSlice, nblocks - b0), c->tables.as<int32_t>(), s));
+    LZ4MI_TRY(lz4mi_launch_frames_enc_finish(in, blk_in_off, blk_len, nblocks, finfo, nframes, work, enc_off, comp_len,
+                                             out, out_total, frame_out_off, frame_out_cap, rec_off, pay_off, sum_off,
+                                             pay_len, hash_off, hash_len, hash_dst, flags, s));
     return LZ4MI_OK;
 }
 

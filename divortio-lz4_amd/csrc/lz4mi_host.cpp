@@ -20,6 +20,7 @@
 
 #include "../../include/lz4mi.h"
 #include "lz4mi_frames.h"
+#include "lz4mi_frames_enc.h"
 
 extern "C" __attribute__((visibility("hidden"))) void lz4mi_advise_output(void* p, uint64_t n);   // (lz4mi_capi.cpp)
 
@@ -419,5 +420,93 @@ extern "C" int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* fr
         if (!fi[fr::kErr] && !fi[fr::kDecline]) totals[2] += fi[fr::kTotal];
         if (fi[fr::kDecline]) ++totals[3];
     }
+    return LZ4MI_OK;
+}
+
+// lz4mi_frames_plan / lz4mi_frames_compress on the calling thread (include/lz4mi.h): the same per-frame steps
+// (lz4mi_frames_enc.h) in the device passes' order -- count, exclusive scans, fill; prep, encode, size, position,
+// write, pack, checksums -- with lz4mi_host_compress_block and a fresh table per block as the encoder.
+extern "C" int32_t lz4mi_host_frames_plan(const uint64_t* src_off, const uint64_t* src_len, uint32_t nframes,
+                                          uint32_t block_max, uint64_t* blk_in_off, uint32_t* blk_len,
+                                          uint32_t* blk_frame, uint64_t* blk_work_off, uint32_t cap_blocks,
+                                          int64_t* finfo, int64_t* totals, uint32_t flags) {
+    namespace fe = lz4mi::frames_enc;
+    if (flags & ~fe::kFlags) return LZ4MI_ERR_ARG;
+    if (!finfo || !totals || (nframes && (!src_off || !src_len)) ||
+        (cap_blocks && (!blk_in_off || !blk_len || !blk_frame || !blk_work_off)))
+        return LZ4MI_ERR_ARG;
+    const uint32_t bmax = fe::block_bytes(fe::block_id(block_max));
+    uint64_t blocks = 0, work = fe::kDump;
+    for (uint32_t f = 0; f < nframes; ++f) {
+        int64_t* fi = finfo + 8ull * f;
+        fe::plan_count(src_len[f], bmax, flags, fi);
+        fi[fe::kFirst] = (int64_t)blocks;
+        fi[fe::kPos] = (int64_t)work;
+        blocks += fe::listed(fi);
+        work += fe::listed_work(fi);
+    }
+    totals[0] = (int64_t)blocks;
+    totals[1] = totals[2] = 0;
+    totals[3] = (int64_t)work;
+    for (uint32_t f = 0; f < nframes; ++f) {
+        int64_t* fi = finfo + 8ull * f;
+        fe::plan_fill(src_off[f], f, fi, blk_in_off, blk_len, blk_frame, blk_work_off, cap_blocks);
+        totals[1] += (int64_t)fe::listed(fi);
+        if (!fi[fe::kDecline]) totals[2] += fi[fe::kLen];
+    }
+    return LZ4MI_OK;
+}
+
+extern "C" int32_t lz4mi_host_frames_compress(const uint8_t* in, const uint64_t* blk_in_off, const uint32_t* blk_len,
+                                              const uint32_t* blk_frame, const uint64_t* blk_work_off, uint32_t nblocks,
+                                              int64_t* finfo, uint32_t nframes, uint8_t* work, uint64_t work_bytes,
+                                              uint8_t* out, uint64_t out_total, const uint64_t* frame_out_off,
+                                              const uint64_t* frame_out_cap, uint32_t flags) {
+    namespace fe = lz4mi::frames_enc;
+    if (flags & ~fe::kFlags) return LZ4MI_ERR_ARG;
+    if (fe::bad_compress_args(in, blk_in_off, blk_len, blk_frame, blk_work_off, nblocks, finfo, nframes, work, work_bytes,
+                              out, frame_out_off, frame_out_cap, flags))
+        return LZ4MI_ERR_ARG;
+    for (uint32_t b = 0; b < nblocks; ++b)   // the host sees the lists: every slot inside work[kDump .. work_bytes)
+        if (blk_work_off[b] < fe::kDump || blk_work_off[b] > work_bytes ||
+            fe::slot_bytes(blk_len[b]) > work_bytes - blk_work_off[b])
+            return LZ4MI_ERR_ARG;
+    std::vector<uint64_t> enc_off(nblocks, 0), rec_off(nblocks, fe::kNone), hash_off(nframes, 0), hash_dst(nframes, fe::kNone);
+    std::vector<uint32_t> enc_len(nblocks, 0), comp_len(nblocks, 0), hash_len(nframes, 0);
+    std::vector<int32_t> table(16384);
+    for (uint32_t f = 0; f < nframes; ++f) {
+        int64_t* fi = finfo + 8ull * f;
+        fe::prep_frame(fi, nblocks, blk_len, blk_work_off, work_bytes, enc_off.data(), enc_len.data(), flags);
+        if (fi[fe::kDecline]) continue;
+        for (uint64_t b = (uint64_t)fi[fe::kFirst]; b < (uint64_t)(fi[fe::kFirst] + fi[fe::kCount]); ++b) {
+            std::fill(table.begin(), table.end(), 0);
+            const int64_t r = lz4mi_host_compress_block(in + blk_in_off[b], enc_len[b], 0, (int32_t)enc_len[b], table.data(),
+                                                        work + enc_off[b], lz4mi_compress_bound(enc_len[b]), 0);
+            if (r < 0) return (int32_t)r;
+            comp_len[b] = (uint32_t)r;
+        }
+        fe::size_frame(fi, blk_len, comp_len.data());
+    }
+    uint64_t at = 0;
+    for (uint32_t f = 0; f < nframes; ++f) {
+        int64_t* fi = finfo + 8ull * f;
+        if (flags & LZ4MI_FRAMES_PACKED) at = fe::pack_frame(fi, at, out_total);
+        else fe::place_frame(fi, frame_out_off[f], frame_out_cap[f], out_total);
+        fe::write_frame(fi, out, blk_in_off, blk_len, comp_len.data(), rec_off.data(), &hash_off[f], &hash_len[f], &hash_dst[f]);
+    }
+    auto put32 = [&](uint64_t pos, uint32_t v) {
+        for (int k = 0; k < 4; ++k) out[pos + k] = (uint8_t)(v >> (8 * k));
+    };
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        if (rec_off[b] == fe::kNone) continue;
+        const bool st = fe::stored(comp_len[b], blk_len[b]);
+        const uint64_t len = st ? blk_len[b] : comp_len[b];
+        put32(rec_off[b], st ? (blk_len[b] | 0x80000000u) : comp_len[b]);
+        if (len) std::memcpy(out + rec_off[b] + 4, st ? in + blk_in_off[b] : work + enc_off[b], len);
+        if (flags & LZ4MI_BLOCK_CHECKSUM)
+            put32(rec_off[b] + 4 + len, lz4mi_xxh32(out + rec_off[b] + 4, len, 0, LZ4MI_XXH_STANDARD));
+    }
+    for (uint32_t f = 0; f < nframes; ++f)
+        if (hash_dst[f] != fe::kNone) put32(hash_dst[f], lz4mi_xxh32(in + hash_off[f], hash_len[f], 0, 0));
     return LZ4MI_OK;
 }

@@ -141,4 +141,22 @@ hipError_t lz4mi_launch_frames_finish(int64_t* finfo, uint32_t nframes, uint32_t
                                       uint64_t* hash_off, uint32_t* hash_len, uint32_t* hashed, uint32_t* digest,
                                       uint32_t flags, hipStream_t stream);
 
+// ---- frame batches, encode side (lz4mi_frames_enc.hip): the plan; the pass before the batch encoder (enc_off /
+// enc_len: the encoder's lists, zeroed by the caller); everything behind it (rec_off, sum_off, hash_dst set to
+// ~0 and pay_len, hash_len to 0 by the caller; lz4mi_launch_xxh32 stores no digest at ~0)
+hipError_t lz4mi_launch_frames_plan(const uint64_t* src_off, const uint64_t* src_len, uint32_t nframes, uint32_t bmax,
+                                    uint64_t* blk_in_off, uint32_t* blk_len, uint32_t* blk_frame, uint64_t* blk_work_off,
+                                    uint32_t cap_blocks, int64_t* finfo, int64_t* totals, uint32_t flags,
+                                    hipStream_t stream);
+hipError_t lz4mi_launch_frames_enc_prep(int64_t* finfo, uint32_t nframes, uint32_t nblocks, const uint32_t* blk_len,
+                                        const uint64_t* blk_work_off, uint64_t work_bytes, uint64_t* enc_off,
+                                        uint32_t* enc_len, uint32_t flags, hipStream_t stream);
+hipError_t lz4mi_launch_frames_enc_finish(const uint8_t* in, const uint64_t* blk_in_off, const uint32_t* blk_len,
+                                          uint32_t nblocks, int64_t* finfo, uint32_t nframes, const uint8_t* work,
+                                          const uint64_t* enc_off, const uint32_t* comp_len, uint8_t* out,
+                                          uint64_t out_total, const uint64_t* frame_out_off,
+                                          const uint64_t* frame_out_cap, uint64_t* rec_off, uint64_t* pay_off,
+                                          uint64_t* sum_off, uint32_t* pay_len, uint64_t* hash_off, uint32_t* hash_len,
+                                          uint64_t* hash_dst, uint32_t flags, hipStream_t stream);
+
 }  // extern "C"

@@ -89,7 +89,8 @@ __device__ __forceinline__ uint32_t finish(uint32_t v1, uint32_t v2, uint32_t v3
 }
 
 // hashes[buf] = digest; or (TO_FRAME) the digest stored little-endian at dst + dst_off[buf]
-// (frame block checksums written after their payloads). Two instantiations, so the plain
+// (frame block checksums written after their payloads; dst_off[buf] == ~0: nothing is stored,
+// lz4mi_frames_enc.hip). Two instantiations, so the plain
 // batch kernel keeps its register allocation.
 template <bool TO_FRAME>
 __global__ __launch_bounds__(256) void lz4mi_xxh32_kernel(const uint8_t* in, const uint64_t* off, const uint32_t* len,
@@ -113,6 +114,7 @@ __global__ __launch_bounds__(256) void lz4mi_xxh32_kernel(const uint8_t* in, con
     uint32_t v1 = __shfl(v, qb + 0, 64), v2 = __shfl(v, qb + 1, 64), v3 = __shfl(v, qb + 2, 64),
              v4 = __shfl(v, qb + 3, 64);
     if (!live || j != 0) return;
+    if (TO_FRAME && dst_off[buf] == ~0ull) return;   // (no place: a block or frame of a batch that is not written)
     const uint32_t h = finish(v1, v2, v3, v4, p, L, seed, standard);
     if (TO_FRAME) {
         uint8_t* q8 = dst + dst_off[buf];

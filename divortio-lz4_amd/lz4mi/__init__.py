@@ -35,8 +35,12 @@ LINKED_EXACT = 0x100
 VERIFY_BLOCKS = 0x200
 VERIFY_CONTENT = 0x400
 FRAMES_MEASURE = 0x800
+FRAMES_CONTENT_CHECKSUM = 0x1000
+FRAMES_NO_CONTENT_SIZE = 0x2000
+FRAMES_DEPENDENT = 0x4000
+FRAMES_PACKED = 0x8000
 
-# finfo[f][7] of the frame batch calls (include/lz4mi.h LZ4MI_FRAMES_DECLINE_*)
+# finfo[f][7] of the frame batch calls, decode and encode (include/lz4mi.h LZ4MI_FRAMES_DECLINE_*)
 (DECLINE_CAP_BLOCKS, DECLINE_PAST_END, DECLINE_EMPTY, DECLINE_UNSIZED_EXACT, DECLINE_MEASURE, DECLINE_SIZE_MISMATCH,
  DECLINE_OUT_CAP, DECLINE_LAYOUT, DECLINE_DEPENDENT, DECLINE_HASH_4G) = range(1, 11)
 
@@ -55,7 +59,8 @@ EXPORTS = ("lz4mi_status_message", "lz4mi_init", "lz4mi_device_count", "lz4mi_ve
            "lz4mi_host_compress_block", "lz4mi_host_compress_chain", "lz4mi_host_decompress_block",
            "lz4mi_decoded_sizes", "lz4mi_host_decoded_size", "lz4mi_host_block_read_end",
            "lz4mi_verify_blocks", "lz4mi_host_verify_blocks", "lz4mi_frames_index", "lz4mi_frames_decompress",
-           "lz4mi_host_frames_index")
+           "lz4mi_host_frames_index", "lz4mi_frame_bound", "lz4mi_frames_plan", "lz4mi_frames_compress",
+           "lz4mi_host_frames_plan", "lz4mi_host_frames_compress")
 
 
 class Lz4miError(RuntimeError):
@@ -143,6 +148,19 @@ def lib():
         L.lz4mi_host_frames_index.restype = ctypes.c_int32
         L.lz4mi_host_frames_index.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
                                               _vp, ctypes.c_uint32]
+        L.lz4mi_frame_bound.restype = ctypes.c_uint64
+        L.lz4mi_frame_bound.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+        plan = [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32]
+        comp = [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64,
+                _vp, _vp, ctypes.c_uint32]
+        L.lz4mi_frames_plan.restype = ctypes.c_int32
+        L.lz4mi_frames_plan.argtypes = plan + [_vp]
+        L.lz4mi_host_frames_plan.restype = ctypes.c_int32
+        L.lz4mi_host_frames_plan.argtypes = plan
+        L.lz4mi_frames_compress.restype = ctypes.c_int32
+        L.lz4mi_frames_compress.argtypes = comp + [_vp]
+        L.lz4mi_host_frames_compress.restype = ctypes.c_int32
+        L.lz4mi_host_frames_compress.argtypes = comp
         L.lz4mi_generate_blocks.restype = ctypes.c_int32
         L.lz4mi_generate_blocks.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                             ctypes.c_uint32, _vp]
@@ -496,6 +514,58 @@ def host_frames_index(arena, frame_off, frame_len, cap_blocks, measure=False, js
     return res
 
 
+def frame_bound(n, block_max=4194304):
+    """lz4mi_frame_bound: no frame of the frame batch encoder for n source bytes is longer."""
+    return int(lib().lz4mi_frame_bound(int(n), int(block_max) & 0xFFFFFFFF))
+
+
+def frames_enc_flags(independent=True, content_checksum=False, add_content_size=True, block_checksum=False,
+                     packed=False):
+    """The flags of lz4mi_frames_plan / lz4mi_frames_compress (without LZ4MI_DEVICE_PTRS)."""
+    return ((0 if independent else FRAMES_DEPENDENT) | (FRAMES_CONTENT_CHECKSUM if content_checksum else 0) |
+            (0 if add_content_size else FRAMES_NO_CONTENT_SIZE) | (BLOCK_CHECKSUM if block_checksum else 0) |
+            (FRAMES_PACKED if packed else 0))
+
+
+def host_frames_plan(src_off, src_len, block_max, cap_blocks, flags=0):
+    """lz4mi_frames_plan on the calling thread (lz4mi_host_frames_plan, no device needed) -> dict with finfo
+    (nframes x 8 int64), totals (4 int64) and the block lists blk_in_off / blk_len / blk_frame / blk_work_off
+    (cap_blocks entries each, the first totals[1] of them written). flags: frames_enc_flags()."""
+    off = np.ascontiguousarray(src_off, dtype=np.uint64)
+    ln = np.ascontiguousarray(src_len, dtype=np.uint64)
+    assert off.ndim == 1 and off.shape == ln.shape
+    n = off.size
+    res = {"finfo": np.zeros((n, 8), dtype=np.int64), "totals": np.zeros(4, dtype=np.int64),
+           "blk_in_off": np.zeros(cap_blocks, dtype=np.uint64), "blk_len": np.zeros(cap_blocks, dtype=np.uint32),
+           "blk_frame": np.zeros(cap_blocks, dtype=np.uint32), "blk_work_off": np.zeros(cap_blocks, dtype=np.uint64)}
+    _check(lib().lz4mi_host_frames_plan(_p(off), _p(ln), n, int(block_max) & 0xFFFFFFFF, _p(res["blk_in_off"]),
+                                        _p(res["blk_len"]), _p(res["blk_frame"]), _p(res["blk_work_off"]), cap_blocks,
+                                        res["finfo"].ctypes.data, res["totals"].ctypes.data, flags))
+    return res
+
+
+def host_frames_compress(arena, plan, out, flags=0, slots=None, work=None):
+    """lz4mi_frames_compress on the calling thread (lz4mi_host_frames_compress, no device needed): the frames of
+    `plan` (host_frames_plan's result over ranges of `arena`; its finfo is updated in place) into `out` (numpy
+    uint8, written in place). slots: (frame_out_off, frame_out_cap), or None with FRAMES_PACKED in flags.
+    work: the scratch (numpy uint8; default: totals[3] bytes). Returns finfo."""
+    a = _u8(arena)
+    assert out.dtype == np.uint8 and out.flags.c_contiguous
+    nb = int(plan["totals"][1])
+    if work is None:
+        work = np.zeros(int(plan["totals"][3]), dtype=np.uint8)
+    so = sc = None
+    if slots is not None:
+        so = np.ascontiguousarray(slots[0], dtype=np.uint64)
+        sc = np.ascontiguousarray(slots[1], dtype=np.uint64)
+    fi = plan["finfo"]
+    _check(lib().lz4mi_host_frames_compress(_p(a), _p(plan["blk_in_off"]), _p(plan["blk_len"]), _p(plan["blk_frame"]),
+                                            _p(plan["blk_work_off"]), nb, fi.ctypes.data, fi.shape[0], _p(work),
+                                            work.size, out.ctypes.data, out.size, None if so is None else _p(so),
+                                            None if sc is None else _p(sc), flags))
+    return fi
+
+
 # -------------------------------------------------------------- device API
 # Raw device pointers (ints, e.g. torch tensor .data_ptr()) and a hipStream_t
 # handle (int, e.g. torch.cuda.current_stream().cuda_stream). Async.
@@ -575,6 +645,26 @@ def frames_decompress_dev(in_ptr, blk_in_off_ptr, blk_word_ptr, blk_frame_ptr, b
                                          finfo_ptr, nframes, out_ptr, frame_out_off_ptr, frame_out_cap_ptr,
                                          DEVICE_PTRS | (JS_EXACT if js_exact else 0) |
                                          (VERIFY_CONTENT if verify_content else 0), stream or None))
+
+
+def frames_plan_dev(src_off_ptr, src_len_ptr, nframes, block_max, blk_in_off_ptr, blk_len_ptr, blk_frame_ptr,
+                    blk_work_off_ptr, cap_blocks, finfo_ptr, totals_ptr, stream=0, flags=0):
+    """Block plan of a batch of device-resident buffers (include/lz4mi.h lz4mi_frames_plan): device pointers,
+    asynchronous on `stream`, nothing read back. flags: frames_enc_flags()."""
+    _check(lib().lz4mi_frames_plan(src_off_ptr, src_len_ptr, nframes, int(block_max) & 0xFFFFFFFF, blk_in_off_ptr,
+                                   blk_len_ptr, blk_frame_ptr, blk_work_off_ptr, cap_blocks, finfo_ptr, totals_ptr,
+                                   DEVICE_PTRS | flags, stream or None))
+
+
+def frames_compress_dev(in_ptr, blk_in_off_ptr, blk_len_ptr, blk_frame_ptr, blk_work_off_ptr, nblocks, finfo_ptr,
+                        nframes, work_ptr, work_bytes, out_ptr, out_total, frame_out_off_ptr=None,
+                        frame_out_cap_ptr=None, stream=0, flags=0):
+    """Compress the buffers lz4mi_frames_plan listed into one frame each, in one call (include/lz4mi.h
+    lz4mi_frames_compress): device pointers, asynchronous on `stream`; finfo holds each frame's length, position
+    and decline code afterwards. flags: frames_enc_flags(), the plan's; with packed the slot arrays may be None."""
+    _check(lib().lz4mi_frames_compress(in_ptr, blk_in_off_ptr, blk_len_ptr, blk_frame_ptr, blk_work_off_ptr, nblocks,
+                                       finfo_ptr, nframes, work_ptr, work_bytes, out_ptr, out_total, frame_out_off_ptr,
+                                       frame_out_cap_ptr, DEVICE_PTRS | flags, stream or None))
 
 
 def generate_blocks_dev(out_ptr, kind, seed0, block_size, nblocks, stream=0):

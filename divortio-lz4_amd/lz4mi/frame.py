@@ -1246,3 +1246,117 @@ def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measu
                 raise err
             res[f] = err
     return res
+
+
+def _frame_alone(one, block_size, independent, content_checksum, add_content_size, block_checksum, stream):
+    """One frame of a device-resident buffer outside the batch (what compress_frames_device does with a frame
+    the batch declines) -> (frame, route). A dependent frame of more than one block is one chain
+    (lz4mi.compress_chain over the host copy, bufferCompress.js:182-236), route "chain"; anything else the
+    per-frame device path (DeviceCodec), route "codec". The content checksum is hashed on the host."""
+    import torch
+    import lz4mi
+    n = one.numel()
+    dev = one.device
+    hdr = header(block_size, independent, content_checksum, n if add_content_size else None, None, block_checksum)
+    host = None
+    if not independent and n > block_size:
+        route = "chain"
+        host = one.cpu().numpy()
+        parts = []
+        for k, comp in enumerate(lz4mi.compress_chain(host, 0, n, block_size, np.zeros(16384, dtype=np.int32))):
+            raw = host[k * block_size:(k + 1) * block_size]
+            pay, word = (comp, comp.size) if 0 < comp.size < raw.size else (raw, raw.size | 0x80000000)
+            parts += [np.array([word], dtype="<u4").view(np.uint8), pay]
+            if block_checksum:
+                parts.append(np.array([lz4mi.xxh32(pay, standard=True)], dtype="<u4").view(np.uint8))
+        body = torch.from_numpy(np.concatenate(parts)).to(dev)
+    else:
+        route = "codec"
+        body = DeviceCodec(stream).records(one, block_size, block_checksum)
+    tail = b"\x00\x00\x00\x00"
+    if content_checksum:
+        h = lz4mi.XXHash32(0, len64=True)
+        if host is not None:
+            h.update(host)
+        else:
+            for p in range(0, n, CHECKSUM_PIECE):
+                h.update(one[p:p + CHECKSUM_PIECE].cpu().numpy())
+        tail += int(h.digest()).to_bytes(4, "little")
+    out = torch.empty(len(hdr) + body.numel() + len(tail), dtype=torch.uint8, device=dev)
+    out[:len(hdr)] = torch.frombuffer(bytearray(hdr), dtype=torch.uint8).to(dev)
+    out[len(hdr):len(hdr) + body.numel()] = body
+    out[len(hdr) + body.numel():] = torch.frombuffer(bytearray(tail), dtype=torch.uint8).to(dev)
+    return out, route
+
+
+def compress_frames_device(buffers, block_size=4194304, independent=True, content_checksum=False,
+                           add_content_size=True, block_checksum=False, stream=None, report=None, offsets=None,
+                           lengths=None):
+    """Compress a batch of device-resident buffers into one LZ4 frame each with one plan call, one scratch and one
+    output allocation and one compress call (lz4mi_frames_plan / lz4mi_frames_compress, packed): frame f is
+    LZ4.compress(buffer f, null, block_size, independent, content_checksum, add_content_size) byte for byte
+    (block_checksum adds FLG 0x10 and the records' checksums, which the reference never writes). The blocks of all
+    buffers go into the batch encoder, the frames are laid out and written on the device, and the checksums are
+    hashed there, one chain per block or frame, all in one launch each.
+
+    buffers: a list of 1-D uint8 CUDA tensors, or one such tensor holding buffer f at
+    buffers[offsets[f] : offsets[f] + lengths[f]] (any alignment). The list form concatenates the buffers first,
+    a device copy of all input: buffers that already lie in one tensor should be passed with offsets and lengths.
+    Two host synchronisations: finfo and totals read back after the plan, finfo after the compress call.
+    A frame the batch declines (finfo[f][7]) is completed alone, so the result is always complete: a dependent
+    frame of more than one block by one chain (lz4mi.compress_chain), anything else by DeviceCodec, each with
+    header(). report (a dict, optional) receives routes (per frame "batch", "chain" or "codec") and declined (per
+    frame the decline code). Returns the list of frames (uint8 CUDA tensors): batch frames are views of the one
+    allocation, back to back."""
+    import torch
+    import lz4mi
+    if offsets is None:
+        buffers = list(buffers)
+        lens = [int(t.numel()) for t in buffers]
+        offs = [0] * len(lens)
+        for k in range(1, len(lens)):
+            offs[k] = offs[k - 1] + lens[k - 1]
+        dev = buffers[0].device if buffers else torch.device("cuda", torch.cuda.current_device())
+    else:
+        offs, lens = [int(x) for x in offsets], [int(x) for x in lengths]
+        dev = buffers.device
+    nf = len(lens)
+    if report is None:
+        report = {}
+    report.update(routes=[None] * nf, declined=[0] * nf)
+    if nf == 0:
+        return []
+    bs = {4: 65536, 5: 262144, 6: 1048576, 7: 4194304}[block_id(block_size)]
+    flags = lz4mi.frames_enc_flags(independent, content_checksum, add_content_size, block_checksum, packed=True)
+    lz4mi.init(dev.index if dev.index is not None else torch.cuda.current_device())
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        arena = torch.cat(buffers) if offsets is None else buffers
+        if arena.numel() == 0:
+            arena = torch.zeros(1, dtype=torch.uint8, device=dev)
+        span = torch.tensor([offs, lens], dtype=torch.int64, device=dev)
+        cap = max(1, sum(-(-n // bs) for n in lens))     # the lengths are the host's: the exact block count
+        blk64 = torch.empty((2, cap), dtype=torch.int64, device=dev)   # in_off, work_off
+        blk32 = torch.empty((2, cap), dtype=torch.int32, device=dev)   # len, frame
+        fin = torch.zeros(8 * nf + 4, dtype=torch.int64, device=dev)   # finfo, then totals
+        lz4mi.frames_plan_dev(span[0].data_ptr(), span[1].data_ptr(), nf, bs, blk64[0].data_ptr(), blk32[0].data_ptr(),
+                              blk32[1].data_ptr(), blk64[1].data_ptr(), cap, fin.data_ptr(), fin.data_ptr() + 64 * nf,
+                              s.cuda_stream, flags=flags)
+        totals = fin[8 * nf:].cpu().tolist()
+        listed, out_total, work_bytes = int(totals[1]), int(totals[2]), int(totals[3])
+        work = torch.empty(max(16, work_bytes), dtype=torch.uint8, device=dev)
+        out = torch.empty(max(1, out_total), dtype=torch.uint8, device=dev)
+        lz4mi.frames_compress_dev(arena.data_ptr(), blk64[0].data_ptr(), blk32[0].data_ptr(), blk32[1].data_ptr(),
+                                  blk64[1].data_ptr(), listed, fin.data_ptr(), nf, work.data_ptr(), work.numel(),
+                                  out.data_ptr(), out_total, None, None, s.cuda_stream, flags=flags)
+        done = fin[:8 * nf].cpu().numpy().reshape(nf, 8)
+    res = [None] * nf
+    for f in range(nf):
+        if done[f, 7]:
+            report["declined"][f] = int(done[f, 7])
+            res[f], report["routes"][f] = _frame_alone(arena[offs[f]:offs[f] + lens[f]], bs, independent,
+                                                       content_checksum, add_content_size, block_checksum, stream)
+        else:
+            report["routes"][f] = "batch"
+            res[f] = out[int(done[f, 5]):int(done[f, 5] + done[f, 3])]
+    return res

@@ -89,8 +89,14 @@ extern "C" {
 #define LZ4MI_FRAMES_MEASURE 0x800u /* lz4mi_frames_index: measure every frame's block sizes (lz4mi_decoded_sizes),
                                     also where a content size would give them from the reference encoder's layout:
                                     for frames with partial blocks in the middle. */
+/* lz4mi_frames_plan / lz4mi_frames_compress (and their host twins): */
+#define LZ4MI_FRAMES_CONTENT_CHECKSUM 0x1000u /* FLG 0x04: the reference's XXH32 variant of the source behind the EndMark */
+#define LZ4MI_FRAMES_NO_CONTENT_SIZE 0x2000u  /* leave the content size field out (default: written, like the reference) */
+#define LZ4MI_FRAMES_DEPENDENT 0x4000u        /* FLG without 0x20 (the reference's default): frames of at most one block */
+#define LZ4MI_FRAMES_PACKED 0x8000u           /* lz4mi_frames_compress: the frames back to back from out[0] */
 
-/* ---- why lz4mi_frames_index / lz4mi_frames_decompress leave a frame to the caller (finfo[f][7]) ---- */
+/* ---- why lz4mi_frames_index / lz4mi_frames_decompress (and lz4mi_frames_plan / lz4mi_frames_compress) leave a
+ *      frame to the caller (finfo[f][7]) ---- */
 #define LZ4MI_FRAMES_DECLINE_CAP_BLOCKS 1    /* its blocks are not in the lists: cap_blocks (nblocks) too small */
 #define LZ4MI_FRAMES_DECLINE_PAST_END 2      /* the walk of its size words ran past the frame's end (a cut frame) */
 #define LZ4MI_FRAMES_DECLINE_EMPTY 3         /* no blocks, or the content-size flag with size 0 (the empty frame) */
@@ -505,6 +511,89 @@ int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* frame_off, co
                                 uint32_t nframes, uint64_t* blk_in_off, uint32_t* blk_word, uint32_t* blk_frame,
                                 uint32_t* blk_size, uint32_t cap_blocks, int64_t* finfo, int64_t* totals,
                                 uint32_t flags);
+
+/*
+ * A BATCH OF BUFFERS compressed into one LZ4 frame each on the device: plan, then compress. Device pointers only
+ * (LZ4MI_DEVICE_PTRS required), asynchronous on `stream`, nothing is read back by either call.
+ * Replaces compressBuffer (src/buffer/bufferCompress.js:100-256) called once per buffer with dictionary = null:
+ * frame f is LZ4.compress(in[src_off[f] .. +src_len[f]), null, block_max, true, contentChecksum, addContentSize),
+ * byte for byte (any alignment; nothing outside these ranges is read). block_max is resolved as getBlockId does
+ * (:77-82): 0 or <= 65536 gives 64 KiB, <= 262144 256 KiB, <= 1048576 1 MiB, anything else 4 MiB.
+ * flags (both calls take the same ones): LZ4MI_DEVICE_PTRS | LZ4MI_FRAMES_CONTENT_CHECKSUM (FLG 0x04; one XXH32
+ * chain per frame, all frames hashed in one launch that stores the digests in place; a source of 4 GiB or more is
+ * declined, LZ4MI_FRAMES_DECLINE_HASH_4G) | LZ4MI_FRAMES_NO_CONTENT_SIZE | LZ4MI_BLOCK_CHECKSUM (FLG 0x10: every
+ * record ends with the spec XXH32 of its payload, as in lz4mi_frame_pack; the reference never writes it) |
+ * LZ4MI_FRAMES_DEPENDENT (FLG without 0x20, what LZ4.compress(buf) writes by default: a frame of at most one block
+ * differs from its independent twin in FLG and the header checksum byte only and is written; one with more blocks
+ * is declined, LZ4MI_FRAMES_DECLINE_DEPENDENT: its chain is lz4mi_compress_chain's job) | LZ4MI_FRAMES_PACKED.
+ * Any other flag, a NULL required pointer, NULL lists with cap_blocks (nblocks) > 0 or a `work` of less than 16
+ * bytes with nblocks > 0: LZ4MI_ERR_ARG before the device is looked at.
+ * Out of scope: dictionaries (the reference's prewarm reaches block 0 only; the DictID field is never written),
+ * multi-block dependent frames, a spec-variant content checksum, the N-API / JS layer.
+ *
+ * lz4mi_frames_plan is arithmetic on the lengths (a count, a scan, a fill; one lane per frame). It lists every
+ * frame's blocks in frame order, frame after frame: blk_in_off[b] (absolute in `in`), blk_len[b] = min(block_max,
+ * rest), blk_frame[b], and blk_work_off[b], the block's slot in `work`: slots are lz4mi_compress_bound(blk_len[b])
+ * rounded up to 16 bytes, assigned by an exclusive scan from work[16] on (work[0 .. 16) is where the encoder's
+ * waves of blocks that are not encoded put their one byte), so scratch grows with the data, not with
+ * nblocks x bound(block_max). finfo[f] (8 x int64 per frame):
+ *   [0] 0; [1] FLG | BD << 8; [2] the source length; [3] lz4mi_frame_bound(src_len[f], block_max) after the plan,
+ *   the frame's real length after the compress call; [4] its first block in the lists; [5] 0 after the plan, the
+ *   frame's position in `out` after the compress call; [6] its block count; [7] 0 = the compress call writes the
+ *   frame, else LZ4MI_FRAMES_DECLINE_DEPENDENT / _HASH_4G (neither lists blocks) / _CAP_BLOCKS.
+ * A source of length 0 has no blocks and is not declined: the reference writes header, EndMark and, if asked, the
+ * checksum of nothing, and so does the compress call. The blocks of the frames that fit are listed without gaps,
+ * and a frame whose blocks do not fit cap_blocks lists none. totals (4 x int64): [0] the blocks needed (call again
+ * with that cap_blocks if it is above cap_blocks), [1] the blocks listed, [2] the bytes of `out` that suffice in
+ * packed mode (the sum of [3] over the frames not declined), [3] the bytes of `work` needed for [0] blocks.
+ * Footprint: finfo[0 .. 8 nframes), totals[0 .. 4), and entries [0, totals[1]) of the four lists; nothing else.
+ *
+ * lz4mi_frames_compress takes the lists and finfo as the plan left them (nblocks = cap_blocks or totals[1]) and,
+ * on the one stream: encodes the listed blocks of the frames it will write into `work` with the batch encoder
+ * (lz4mi_compress_blocks' kernel, in slices of at most 4096 blocks: 256 MiB of table scratch per stream); sums
+ * each frame's record sizes with the reference's stored-block rule (0 < comp < raw, else stored) into finfo[f][3];
+ * places the frames; writes every header (its checksum byte included), record position, EndMark and checksum
+ * position, one lane per frame; moves every payload once, one wave per block; and fills in the block and content
+ * checksums with the batched XXH32.
+ * Placing: without LZ4MI_FRAMES_PACKED frame f goes to out[frame_out_off[f] ..) and is declined as
+ * LZ4MI_FRAMES_DECLINE_OUT_CAP when it is longer than frame_out_cap[f] or would end behind out_total. With
+ * LZ4MI_FRAMES_PACKED (frame_out_off / frame_out_cap may be NULL) the frames that are written lie back to back
+ * from out[0] in frame order (a carried device scan of their lengths); a frame that would end behind out_total is
+ * declined as OUT_CAP and takes no room. Either way finfo[f][5] is the frame's position.
+ * Also declined here, where only the device sees it: a frame whose finfo does not fit nblocks, or one of whose
+ * blocks has a slot that is not inside work[16 .. work_bytes) (LZ4MI_FRAMES_DECLINE_CAP_BLOCKS); DEPENDENT and
+ * HASH_4G as in the plan, from this call's flags, which also give FLG.
+ * Footprint: finfo; of `out`, only out[finfo[f][5] .. +finfo[f][3]) of the frames that are written (finfo[f][7]
+ * == 0): a declined frame has no byte of `out` written. `work` is scratch; `in` and the lists are read only.
+ */
+/* 23 + n + 8 * blocks(n, block_max), block_max resolved as above: header without DictID (15), EndMark, content
+ * checksum, and per block a size word and a block checksum around at most n payload bytes (a block that does not
+ * shrink is stored). No frame of either call is longer. (An exported function like every other name here: no
+ * device needed.) */
+uint64_t lz4mi_frame_bound(uint64_t n, uint32_t block_max);
+int32_t lz4mi_frames_plan(const uint64_t* src_off, const uint64_t* src_len, uint32_t nframes, uint32_t block_max,
+                          uint64_t* blk_in_off, uint32_t* blk_len, uint32_t* blk_frame, uint64_t* blk_work_off,
+                          uint32_t cap_blocks, int64_t* finfo /* nframes x 8 */, int64_t* totals /* 4 */,
+                          uint32_t flags, void* stream);
+int32_t lz4mi_frames_compress(const uint8_t* in, const uint64_t* blk_in_off, const uint32_t* blk_len,
+                              const uint32_t* blk_frame, const uint64_t* blk_work_off, uint32_t nblocks,
+                              int64_t* finfo, uint32_t nframes, uint8_t* work, uint64_t work_bytes,
+                              uint8_t* out, uint64_t out_total, const uint64_t* frame_out_off,
+                              const uint64_t* frame_out_cap, uint32_t flags, void* stream);
+/*
+ * The same two contracts on the calling thread (host pointers, no device needed; flags without
+ * LZ4MI_DEVICE_PTRS): the checker of the device passes. The encoder is lz4mi_host_compress_block with a fresh
+ * table per block. A `work` that does not hold the slots of the caller's own lists is LZ4MI_ERR_ARG here (the
+ * host sees the lists).
+ */
+int32_t lz4mi_host_frames_plan(const uint64_t* src_off, const uint64_t* src_len, uint32_t nframes, uint32_t block_max,
+                               uint64_t* blk_in_off, uint32_t* blk_len, uint32_t* blk_frame, uint64_t* blk_work_off,
+                               uint32_t cap_blocks, int64_t* finfo, int64_t* totals, uint32_t flags);
+int32_t lz4mi_host_frames_compress(const uint8_t* in, const uint64_t* blk_in_off, const uint32_t* blk_len,
+                                   const uint32_t* blk_frame, const uint64_t* blk_work_off, uint32_t nblocks,
+                                   int64_t* finfo, uint32_t nframes, uint8_t* work, uint64_t work_bytes,
+                                   uint8_t* out, uint64_t out_total, const uint64_t* frame_out_off,
+                                   const uint64_t* frame_out_cap, uint32_t flags);
 
 
 /*
