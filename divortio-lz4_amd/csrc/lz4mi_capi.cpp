@@ -527,6 +527,7 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
                                 const uint64_t* out_off, const uint32_t* out_cap, const uint8_t* dict,
                                 uint32_t dict_len, uint32_t* out_len, int32_t* status, uint32_t nblocks,
                                 uint32_t flags, void* stream) {
+    if (flags & LZ4MI_FRAMES_CHAINS) return LZ4MI_ERR_ARG;   // (the frame batch encoder's alone)
     DeviceGuard dg;
     if (dg.status()) return dg.status();
     const int js = (flags & LZ4MI_JS_COMPAT) ? 1 : 0;
@@ -1136,7 +1137,7 @@ int32_t lz4mi_frames_plan(const uint64_t* src_off, const uint64_t* src_len, uint
                           uint64_t* blk_in_off, uint32_t* blk_len, uint32_t* blk_frame, uint64_t* blk_work_off,
                           uint32_t cap_blocks, int64_t* finfo, int64_t* totals, uint32_t flags, void* stream) {
     namespace fe = lz4mi::frames_enc;
-    if (!(flags & LZ4MI_DEVICE_PTRS) || (flags & ~(LZ4MI_DEVICE_PTRS | fe::kFlags))) return LZ4MI_ERR_ARG;
+    if (!(flags & LZ4MI_DEVICE_PTRS) || fe::bad_flags(flags & ~LZ4MI_DEVICE_PTRS)) return LZ4MI_ERR_ARG;
     if (!finfo || !totals || (nframes && (!src_off || !src_len)) ||
         (cap_blocks && (!blk_in_off || !blk_len || !blk_frame || !blk_work_off)))
         return LZ4MI_ERR_ARG;
@@ -1154,7 +1155,7 @@ int32_t lz4mi_frames_compress(const uint8_t* in, const uint64_t* blk_in_off, con
                               const uint64_t* frame_out_off, const uint64_t* frame_out_cap, uint32_t flags,
                               void* stream) {
     namespace fe = lz4mi::frames_enc;
-    if (!(flags & LZ4MI_DEVICE_PTRS) || (flags & ~(LZ4MI_DEVICE_PTRS | fe::kFlags))) return LZ4MI_ERR_ARG;
+    if (!(flags & LZ4MI_DEVICE_PTRS) || fe::bad_flags(flags & ~LZ4MI_DEVICE_PTRS)) return LZ4MI_ERR_ARG;
     if (fe::bad_compress_args(in, blk_in_off, blk_len, blk_frame, blk_work_off, nblocks, finfo, nframes, work, work_bytes,
                               out, frame_out_off, frame_out_cap, flags))
         return LZ4MI_ERR_ARG;
@@ -1187,6 +1188,10 @@ int32_t lz4mi_frames_compress(const uint8_t* in, const uint64_t* blk_in_off, con
     for (uint32_t b0 = 0; b0 < nblocks; b0 += fe::kSlice)
         LZ4MI_TRY(lz4mi_launch_compress(in, blk_in_off + b0, enc_len + b0, work, enc_off + b0, comp_len + b0,
                                         std::min(fe::kSlice, nblocks - b0), c->tables.as<int32_t>(), s));
+    // the chains, one workgroup per frame, behind the batch encoder: its waves have written a comp_len for the
+    // chains' blocks too (blocks of length 0 at the dump slot), which the chain pass replaces
+    if (nb && (flags & LZ4MI_FRAMES_CHAINS))
+        LZ4MI_TRY(lz4mi_launch_compress_chains(in, blk_in_off, blk_work_off, finfo, nframes, work, enc_off, comp_len, s));
     LZ4MI_TRY(lz4mi_launch_frames_enc_finish(in, blk_in_off, blk_len, nblocks, finfo, nframes, work, enc_off, comp_len,
                                              out, out_total, frame_out_off, frame_out_cap, rec_off, pay_off, sum_off,
                                              pay_len, hash_off, hash_len, hash_dst, flags, s));

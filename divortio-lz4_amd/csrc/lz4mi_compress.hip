@@ -8,13 +8,16 @@
 // depends on the previous one, so each block is one wave walking that chain
 // exactly; the wave's 64 lanes make each step wide (speculative probe batches,
 // 128-byte window compares, emission) instead of making the chain parallel.
-// Two kernels:
+// Three kernels:
 //   lz4mi_compress_gts_kernel    independent blocks, one wave per block, 16 per CU
 //                                (global 15-bit tables + LDS epoch codes);
 //   lz4mi_compress_chain_kernel  dependent blocks / one block with the caller's
 //                                table (LZ4.compressRaw): one wave, the table, the
-//                                source window and the output ring in LDS.
+//                                source window and the output ring in LDS;
+//   lz4mi_compress_chains_kernel the dependent frames of a frame batch: that walk, one
+//                                workgroup per frame, one chain per CU at a time.
 #include "lz4mi_common.h"
+#include "lz4mi_frames_enc.h"
 #include "lz4mi_launch.h"
 
 #include <cstdlib>
@@ -1154,6 +1157,50 @@ __global__ __launch_bounds__(64) void lz4mi_compress_chain_kernel(ChainArgs a) {
     for (int k = lane; k < 16384; k += kWave) a.table[k] = g_ctab[k];
 }
 
+// The chains of a frame batch (lz4mi_frames_compress with LZ4MI_FRAMES_CHAINS): the same walk, one workgroup of one
+// wave per frame, all frames of the batch in one launch. The LDS state (table, source ring, output ring: 157 KiB)
+// leaves room for one workgroup per CU, so a CU walks one chain at a time and takes the next frame when it is
+// done. A frame's table starts as zeros and is not kept; its positions count from the frame's first byte, and
+// CompJob::src_total is the frame's length: nothing behind the frame is read. The frame's base may have any
+// alignment: the ring's 16-byte pieces are aligned in the ring (positions from the base), and the global side of
+// every 16-byte load is a byte-pointer memcpy, for which the compiler assumes no alignment.
+struct ChainsArgs {
+    const uint8_t* in;
+    const uint64_t* blk_in_off;
+    const uint64_t* blk_work_off;
+    const int64_t* finfo;
+    uint8_t* work;
+    uint64_t* enc_off;
+    uint32_t* comp_len;
+    uint32_t nframes;
+};
+
+__global__ __launch_bounds__(64) void lz4mi_compress_chains_kernel(ChainsArgs a) {
+    namespace fe = frames_enc;
+    __shared__ ChainShared F;
+    const uint32_t f = blockIdx.x;
+    if (f >= a.nframes) return;
+    const int64_t* fi = a.finfo + 8ull * f;
+    if (!fe::is_chain(fi)) return;   // declined, at most one block (the batch encoder's) or independent
+    const int lane = threadIdx.x;
+    for (int k = lane; k < 16384; k += kWave) g_ctab[k] = 0;
+    __syncthreads();
+    const uint64_t first = (uint64_t)fi[fe::kFirst], count = (uint64_t)fi[fe::kCount], size = (uint64_t)fi[fe::kSize];
+    const uint32_t bmax = fe::block_max(fi);
+    const uint8_t* src = a.in + a.blk_in_off[first];
+    Ring r{0, 0};
+    for (uint64_t b = 0; b < count; ++b) {
+        const uint32_t n = fe::chain_len(size, bmax, b);
+        const uint64_t slot = a.blk_work_off[first + b];
+        CompJob j{src, size, (int32_t)(b * bmax), (int32_t)n, a.work + slot, (uint64_t)n + n / 255u + 16u, 0, nullptr};
+        const int64_t w = compress_block_chain2(j, F, lane, r);
+        if (lane == 0) {
+            a.comp_len[first + b] = (uint32_t)w;
+            a.enc_off[first + b] = slot;
+        }
+    }
+}
+
 }  // namespace lz4mi
 
 #if LZ4MI_CTIMELINE
@@ -1196,5 +1243,15 @@ extern "C" hipError_t lz4mi_launch_compress_chain(const uint8_t* src, uint64_t s
     if (nblocks == 0) return hipSuccess;
     lz4mi::ChainArgs a{src, src_total, start, len, bsize, table, out, out_off, comp_len, nblocks};
     hipLaunchKernelGGL(lz4mi::lz4mi_compress_chain_kernel, dim3(1), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lz4mi_launch_compress_chains(const uint8_t* in, const uint64_t* blk_in_off,
+                                                   const uint64_t* blk_work_off, const int64_t* finfo, uint32_t nframes,
+                                                   uint8_t* work, uint64_t* enc_off, uint32_t* comp_len,
+                                                   hipStream_t stream) {
+    if (nframes == 0) return hipSuccess;
+    lz4mi::ChainsArgs a{in, blk_in_off, blk_work_off, finfo, work, enc_off, comp_len, nframes};
+    hipLaunchKernelGGL(lz4mi::lz4mi_compress_chains_kernel, dim3(nframes), dim3(64), 0, stream, a);
     return hipGetLastError();
 }

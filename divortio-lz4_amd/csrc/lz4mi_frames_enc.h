@@ -25,7 +25,11 @@ constexpr uint64_t kDump = 16;      // work[0 .. kDump): where the encoder's wav
 constexpr uint32_t kSlice = 4096;   // blocks per encoder launch: 64 KiB of table scratch each
 // the flags of both calls besides LZ4MI_DEVICE_PTRS
 constexpr uint32_t kFlags = LZ4MI_FRAMES_CONTENT_CHECKSUM | LZ4MI_FRAMES_NO_CONTENT_SIZE | LZ4MI_BLOCK_CHECKSUM |
-                            LZ4MI_FRAMES_DEPENDENT | LZ4MI_FRAMES_PACKED;
+                            LZ4MI_FRAMES_DEPENDENT | LZ4MI_FRAMES_PACKED | LZ4MI_FRAMES_CHAINS;
+// a flag neither call knows, or chains under an independent FLG (a broken frame): LZ4MI_ERR_ARG
+inline bool bad_flags(uint32_t flags) {
+    return (flags & ~kFlags) || ((flags & LZ4MI_FRAMES_CHAINS) && !(flags & LZ4MI_FRAMES_DEPENDENT));
+}
 
 // what lz4mi_frames_compress and its host twin refuse as LZ4MI_ERR_ARG before anything is looked at
 inline bool bad_compress_args(const void* in, const void* blk_in_off, const void* blk_len, const void* blk_frame,
@@ -101,9 +105,18 @@ LZ4MI_HD uint32_t write_header(uint8_t* dst, uint32_t flg, uint32_t bd, uint64_t
 }
 
 // ------------------------------------------------------------------------------------------------ plan
+// a dependent frame of more than one block is a chain: one table carried across its blocks, positions int32 from
+// the frame's first byte (table values position + 1)
+LZ4MI_HD bool chain_of(uint64_t count, uint32_t flags) { return (flags & LZ4MI_FRAMES_DEPENDENT) && count > 1; }
+// block k of a chain over `size` bytes: src[k * bmax, +chain_len)
+LZ4MI_HD uint32_t chain_len(uint64_t size, uint32_t bmax, uint64_t k) {
+    const uint64_t rest = size - k * bmax;
+    return (uint32_t)(rest < bmax ? rest : bmax);
+}
 // the declines that the lengths and the flags alone decide
 LZ4MI_HD int64_t decline_of(uint64_t n, uint64_t count, uint32_t flags) {
-    if ((flags & LZ4MI_FRAMES_DEPENDENT) && count > 1) return LZ4MI_FRAMES_DECLINE_DEPENDENT;
+    if (chain_of(count, flags) && (!(flags & LZ4MI_FRAMES_CHAINS) || n >= 0x7FFFFFFFull))
+        return LZ4MI_FRAMES_DECLINE_DEPENDENT;
     if ((flags & LZ4MI_FRAMES_CONTENT_CHECKSUM) && n > 0xFFFFFFFFull) return LZ4MI_FRAMES_DECLINE_HASH_4G;
     return 0;
 }
@@ -148,7 +161,8 @@ LZ4MI_HD void plan_fill(uint64_t src_off, uint32_t fidx, int64_t* fi, uint64_t* 
 // -------------------------------------------------------------------------------------------- compress
 // Before the encode: FLG from the call's flags, the declines only this call can see, and the frame's blocks into
 // the encoder's lists (the caller has zeroed enc_off / enc_len: a block of a frame that is not written stays a
-// block of length 0 at work[0], the dump slot).
+// block of length 0 at work[0], the dump slot). The blocks of a chain (LZ4MI_FRAMES_CHAINS) stay such blocks too:
+// the chain pass encodes them, from blk_len / blk_work_off, and sets their enc_off and comp_len.
 LZ4MI_HD void prep_frame(int64_t* fi, uint32_t nblocks, const uint32_t* blk_len, const uint64_t* blk_work_off,
                          uint64_t work_bytes, uint64_t* enc_off, uint32_t* enc_len, uint32_t flags) {
     if (fi[kDecline]) return;
@@ -169,11 +183,22 @@ LZ4MI_HD void prep_frame(int64_t* fi, uint32_t nblocks, const uint32_t* blk_len,
             return;
         }
     }
+    if (chain_of(n, flags)) {
+        // the chain pass takes its blocks' lengths from the frame's: the lists must say the same (the slots
+        // checked above are the ones it writes)
+        const uint64_t size = (uint64_t)fi[kSize], bmax = block_max(fi);
+        bool same = n == block_count(size, (uint32_t)bmax);
+        for (uint64_t k = 0; same && k < n; ++k) same = blk_len[first + k] == chain_len(size, (uint32_t)bmax, k);
+        if (!same) fi[kDecline] = LZ4MI_FRAMES_DECLINE_CAP_BLOCKS;
+        return;
+    }
     for (uint64_t b = first; b < first + n; ++b) {
         enc_off[b] = blk_work_off[b];
         enc_len[b] = blk_len[b];
     }
 }
+// after prep_frame: the chain pass walks this frame (FLG is the compress call's)
+LZ4MI_HD bool is_chain(const int64_t* fi) { return !fi[kDecline] && fi[kCount] > 1 && !((uint64_t)fi[kHead] & 0x20u); }
 
 // The frame's length from its blocks' compressed sizes.
 LZ4MI_HD void size_frame(int64_t* fi, const uint32_t* blk_len, const uint32_t* comp_len) {

@@ -6,9 +6,10 @@
 // are moved by one wave each. Nothing is read back between the passes:
 //   plan:     count (lane per frame) -> scan of the block counts and slot bytes (one workgroup, carried) -> fill
 //             (lane per frame: the block lists, totals[])
-//   compress: prep (lane per frame: FLG, declines, the encoder's lists) -> the batch encoder, in slices (the
-//             caller: lz4mi_capi.cpp) -> size (lane per frame: the frame's length; its slot in slot mode) ->
-//             position (packed mode: one workgroup, a carried scan of the lengths) -> write (lane per frame:
+//   compress: prep (lane per frame: FLG, declines, the encoder's lists) -> the batch encoder, in slices, then with
+//             LZ4MI_FRAMES_CHAINS the chains of the multi-block dependent frames, one workgroup per frame
+//             (lz4mi_compress.hip; the caller of both: lz4mi_capi.cpp) -> size (lane per frame: the frame's
+//             length; its slot in slot mode) -> position (packed mode: one workgroup, a carried scan of the lengths) -> write (lane per frame:
 //             header, record positions, EndMark, hash list) -> pack (wave per block: size word and payload) ->
 //             lz4mi_launch_xxh32 over the payloads (block checksums) and over the sources (content checksums)
 // The per-frame steps are lz4mi_frames_enc.h, shared with lz4mi_host_frames_plan / lz4mi_host_frames_compress.

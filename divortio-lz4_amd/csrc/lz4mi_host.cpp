@@ -425,13 +425,14 @@ extern "C" int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* fr
 
 // lz4mi_frames_plan / lz4mi_frames_compress on the calling thread (include/lz4mi.h): the same per-frame steps
 // (lz4mi_frames_enc.h) in the device passes' order -- count, exclusive scans, fill; prep, encode, size, position,
-// write, pack, checksums -- with lz4mi_host_compress_block and a fresh table per block as the encoder.
+// write, pack, checksums -- with lz4mi_host_compress_block and a fresh table per block as the encoder, or one
+// table per frame for a chain (LZ4MI_FRAMES_CHAINS).
 extern "C" int32_t lz4mi_host_frames_plan(const uint64_t* src_off, const uint64_t* src_len, uint32_t nframes,
                                           uint32_t block_max, uint64_t* blk_in_off, uint32_t* blk_len,
                                           uint32_t* blk_frame, uint64_t* blk_work_off, uint32_t cap_blocks,
                                           int64_t* finfo, int64_t* totals, uint32_t flags) {
     namespace fe = lz4mi::frames_enc;
-    if (flags & ~fe::kFlags) return LZ4MI_ERR_ARG;
+    if (fe::bad_flags(flags)) return LZ4MI_ERR_ARG;
     if (!finfo || !totals || (nframes && (!src_off || !src_len)) ||
         (cap_blocks && (!blk_in_off || !blk_len || !blk_frame || !blk_work_off)))
         return LZ4MI_ERR_ARG;
@@ -463,7 +464,7 @@ extern "C" int32_t lz4mi_host_frames_compress(const uint8_t* in, const uint64_t*
                                               uint8_t* out, uint64_t out_total, const uint64_t* frame_out_off,
                                               const uint64_t* frame_out_cap, uint32_t flags) {
     namespace fe = lz4mi::frames_enc;
-    if (flags & ~fe::kFlags) return LZ4MI_ERR_ARG;
+    if (fe::bad_flags(flags)) return LZ4MI_ERR_ARG;
     if (fe::bad_compress_args(in, blk_in_off, blk_len, blk_frame, blk_work_off, nblocks, finfo, nframes, work, work_bytes,
                               out, frame_out_off, frame_out_cap, flags))
         return LZ4MI_ERR_ARG;
@@ -478,6 +479,21 @@ extern "C" int32_t lz4mi_host_frames_compress(const uint8_t* in, const uint64_t*
         int64_t* fi = finfo + 8ull * f;
         fe::prep_frame(fi, nblocks, blk_len, blk_work_off, work_bytes, enc_off.data(), enc_len.data(), flags);
         if (fi[fe::kDecline]) continue;
+        if (fe::is_chain(fi)) {   // one table carried across the frame's blocks, positions from the frame's first byte
+            const uint64_t first = (uint64_t)fi[fe::kFirst], size = (uint64_t)fi[fe::kSize];
+            const uint32_t bmax = fe::block_max(fi);
+            std::fill(table.begin(), table.end(), 0);
+            for (uint64_t k = 0; k < (uint64_t)fi[fe::kCount]; ++k) {
+                const uint32_t n = fe::chain_len(size, bmax, k);
+                enc_off[first + k] = blk_work_off[first + k];
+                const int64_t r = lz4mi_host_compress_block(in + blk_in_off[first], size, (int32_t)(k * bmax), (int32_t)n,
+                                                            table.data(), work + enc_off[first + k], lz4mi_compress_bound(n), 0);
+                if (r < 0) return (int32_t)r;
+                comp_len[first + k] = (uint32_t)r;
+            }
+            fe::size_frame(fi, blk_len, comp_len.data());
+            continue;
+        }
         for (uint64_t b = (uint64_t)fi[fe::kFirst]; b < (uint64_t)(fi[fe::kFirst] + fi[fe::kCount]); ++b) {
             std::fill(table.begin(), table.end(), 0);
             const int64_t r = lz4mi_host_compress_block(in + blk_in_off[b], enc_len[b], 0, (int32_t)enc_len[b], table.data(),

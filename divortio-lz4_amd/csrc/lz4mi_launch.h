@@ -102,6 +102,12 @@ hipError_t lz4mi_launch_compress(const uint8_t* in, const uint64_t* in_off, cons
 hipError_t lz4mi_launch_compress_chain(const uint8_t* src, uint64_t src_total, int32_t start, int32_t len,
                                        int32_t bsize, int32_t* table, uint8_t* out, const uint64_t* out_off,
                                        uint32_t* comp_len, uint32_t nblocks, hipStream_t stream);
+// the chains of a frame batch (LZ4MI_FRAMES_CHAINS), behind lz4mi_launch_frames_enc_prep and the batch encoder: one
+// workgroup per frame walks the blocks of a multi-block dependent frame that is written into their slots of `work`
+// and sets their enc_off and comp_len; every other frame's workgroup returns at once
+hipError_t lz4mi_launch_compress_chains(const uint8_t* in, const uint64_t* blk_in_off, const uint64_t* blk_work_off,
+                                        const int64_t* finfo, uint32_t nframes, uint8_t* work, uint64_t* enc_off,
+                                        uint32_t* comp_len, hipStream_t stream);
 hipError_t lz4mi_launch_xxh32(const uint8_t* in, const uint64_t* off, const uint32_t* len, uint32_t seed,
                               uint32_t* hashes, uint32_t n, int standard, uint8_t* dst, const uint64_t* dst_off,
                               hipStream_t stream);

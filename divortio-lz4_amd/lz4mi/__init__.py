@@ -39,6 +39,7 @@ FRAMES_CONTENT_CHECKSUM = 0x1000
 FRAMES_NO_CONTENT_SIZE = 0x2000
 FRAMES_DEPENDENT = 0x4000
 FRAMES_PACKED = 0x8000
+FRAMES_CHAINS = 0x10000
 
 # finfo[f][7] of the frame batch calls, decode and encode (include/lz4mi.h LZ4MI_FRAMES_DECLINE_*)
 (DECLINE_CAP_BLOCKS, DECLINE_PAST_END, DECLINE_EMPTY, DECLINE_UNSIZED_EXACT, DECLINE_MEASURE, DECLINE_SIZE_MISMATCH,
@@ -520,11 +521,13 @@ def frame_bound(n, block_max=4194304):
 
 
 def frames_enc_flags(independent=True, content_checksum=False, add_content_size=True, block_checksum=False,
-                     packed=False):
-    """The flags of lz4mi_frames_plan / lz4mi_frames_compress (without LZ4MI_DEVICE_PTRS)."""
+                     packed=False, chains=False):
+    """The flags of lz4mi_frames_plan / lz4mi_frames_compress (without LZ4MI_DEVICE_PTRS). chains
+    (LZ4MI_FRAMES_CHAINS, only with independent=False): dependent frames of more than one block are written too,
+    one chain per frame."""
     return ((0 if independent else FRAMES_DEPENDENT) | (FRAMES_CONTENT_CHECKSUM if content_checksum else 0) |
             (0 if add_content_size else FRAMES_NO_CONTENT_SIZE) | (BLOCK_CHECKSUM if block_checksum else 0) |
-            (FRAMES_PACKED if packed else 0))
+            (FRAMES_PACKED if packed else 0) | (FRAMES_CHAINS if chains else 0))
 
 
 def host_frames_plan(src_off, src_len, block_max, cap_blocks, flags=0):

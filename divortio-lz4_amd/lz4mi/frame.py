@@ -1291,7 +1291,7 @@ def _frame_alone(one, block_size, independent, content_checksum, add_content_siz
 
 def compress_frames_device(buffers, block_size=4194304, independent=True, content_checksum=False,
                            add_content_size=True, block_checksum=False, stream=None, report=None, offsets=None,
-                           lengths=None):
+                           lengths=None, chains=False):
     """Compress a batch of device-resident buffers into one LZ4 frame each with one plan call, one scratch and one
     output allocation and one compress call (lz4mi_frames_plan / lz4mi_frames_compress, packed): frame f is
     LZ4.compress(buffer f, null, block_size, independent, content_checksum, add_content_size) byte for byte
@@ -1305,7 +1305,8 @@ def compress_frames_device(buffers, block_size=4194304, independent=True, conten
     Two host synchronisations: finfo and totals read back after the plan, finfo after the compress call.
     A frame the batch declines (finfo[f][7]) is completed alone, so the result is always complete: a dependent
     frame of more than one block by one chain (lz4mi.compress_chain), anything else by DeviceCodec, each with
-    header(). report (a dict, optional) receives routes (per frame "batch", "chain" or "codec") and declined (per
+    header(). chains=True (with independent=False; LZ4MI_FRAMES_CHAINS) keeps those dependent frames in the batch
+    instead: one chain per frame, all of them in the one compress call, route "batch". report (a dict, optional) receives routes (per frame "batch", "chain" or "codec") and declined (per
     frame the decline code). Returns the list of frames (uint8 CUDA tensors): batch frames are views of the one
     allocation, back to back."""
     import torch
@@ -1327,7 +1328,8 @@ def compress_frames_device(buffers, block_size=4194304, independent=True, conten
     if nf == 0:
         return []
     bs = {4: 65536, 5: 262144, 6: 1048576, 7: 4194304}[block_id(block_size)]
-    flags = lz4mi.frames_enc_flags(independent, content_checksum, add_content_size, block_checksum, packed=True)
+    flags = lz4mi.frames_enc_flags(independent, content_checksum, add_content_size, block_checksum, packed=True,
+                                   chains=chains)
     lz4mi.init(dev.index if dev.index is not None else torch.cuda.current_device())
     s = stream if stream is not None else torch.cuda.current_stream(dev)
     with torch.cuda.stream(s):

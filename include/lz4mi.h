@@ -92,8 +92,12 @@ extern "C" {
 /* lz4mi_frames_plan / lz4mi_frames_compress (and their host twins): */
 #define LZ4MI_FRAMES_CONTENT_CHECKSUM 0x1000u /* FLG 0x04: the reference's XXH32 variant of the source behind the EndMark */
 #define LZ4MI_FRAMES_NO_CONTENT_SIZE 0x2000u  /* leave the content size field out (default: written, like the reference) */
-#define LZ4MI_FRAMES_DEPENDENT 0x4000u        /* FLG without 0x20 (the reference's default): frames of at most one block */
+#define LZ4MI_FRAMES_DEPENDENT 0x4000u        /* FLG without 0x20 (the reference's default): frames of at most one block,
+                                                 with LZ4MI_FRAMES_CHAINS also the longer ones */
 #define LZ4MI_FRAMES_PACKED 0x8000u           /* lz4mi_frames_compress: the frames back to back from out[0] */
+#define LZ4MI_FRAMES_CHAINS 0x10000u          /* with LZ4MI_FRAMES_DEPENDENT (alone: LZ4MI_ERR_ARG): a frame of more than
+                                                 one block is listed and written too, its blocks encoded in order with
+                                                 one table carried across them, one chain per frame, all chains at once */
 
 /* ---- why lz4mi_frames_index / lz4mi_frames_decompress (and lz4mi_frames_plan / lz4mi_frames_compress) leave a
  *      frame to the caller (finfo[f][7]) ---- */
@@ -525,11 +529,24 @@ int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* frame_off, co
  * record ends with the spec XXH32 of its payload, as in lz4mi_frame_pack; the reference never writes it) |
  * LZ4MI_FRAMES_DEPENDENT (FLG without 0x20, what LZ4.compress(buf) writes by default: a frame of at most one block
  * differs from its independent twin in FLG and the header checksum byte only and is written; one with more blocks
- * is declined, LZ4MI_FRAMES_DECLINE_DEPENDENT: its chain is lz4mi_compress_chain's job) | LZ4MI_FRAMES_PACKED.
+ * is declined, LZ4MI_FRAMES_DECLINE_DEPENDENT: its chain is lz4mi_compress_chain's job) | LZ4MI_FRAMES_PACKED |
+ * LZ4MI_FRAMES_CHAINS (only with LZ4MI_FRAMES_DEPENDENT, else LZ4MI_ERR_ARG: an independent FLG over chained blocks
+ * would be a broken frame). With it a dependent frame of more than one block is listed by the plan and written by
+ * the compress call: its blocks are encoded in order with one hash table carried across them (zeros at the first
+ * block, positions relative to the frame's first byte: compressBlock of bufferCompress.js:182-239 with
+ * blockIndependence = false), the stored-block rule is applied per block afterwards (a stored block has still
+ * updated the table and its raw bytes are history for the next block), and the frame is LZ4.compress(buf, null,
+ * block_max, false, contentChecksum, addContentSize) byte for byte. One workgroup walks each such frame
+ * (lz4mi_compress_chains_kernel, all frames in one launch); frames of at most one block go through the batch
+ * encoder as without the flag. A multi-block source of 0x7FFFFFFF bytes or more stays declined as DEPENDENT (the
+ * chain's positions are int32, table values position + 1). Each call reads its own flags: a plan made with the flag
+ * and a compress call without it declines these frames as DEPENDENT, and a frame the plan declined stays declined.
  * Any other flag, a NULL required pointer, NULL lists with cap_blocks (nblocks) > 0 or a `work` of less than 16
  * bytes with nblocks > 0: LZ4MI_ERR_ARG before the device is looked at.
  * Out of scope: dictionaries (the reference's prewarm reaches block 0 only; the DictID field is never written),
- * multi-block dependent frames, a spec-variant content checksum, the N-API / JS layer.
+ * multi-block dependent frames without LZ4MI_FRAMES_CHAINS or of 0x7FFFFFFF bytes or more, splitting one chain over
+ * several workgroups (the longest chain of a batch is the call's floor), a spec-variant content checksum, the
+ * N-API / JS layer.
  *
  * lz4mi_frames_plan is arithmetic on the lengths (a count, a scan, a fill; one lane per frame). It lists every
  * frame's blocks in frame order, frame after frame: blk_in_off[b] (absolute in `in`), blk_len[b] = min(block_max,
@@ -550,7 +567,8 @@ int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* frame_off, co
  *
  * lz4mi_frames_compress takes the lists and finfo as the plan left them (nblocks = cap_blocks or totals[1]) and,
  * on the one stream: encodes the listed blocks of the frames it will write into `work` with the batch encoder
- * (lz4mi_compress_blocks' kernel, in slices of at most 4096 blocks: 256 MiB of table scratch per stream); sums
+ * (lz4mi_compress_blocks' kernel, in slices of at most 4096 blocks: 256 MiB of table scratch per stream), and with
+ * LZ4MI_FRAMES_CHAINS the blocks of the multi-block dependent frames with one chain per frame instead; sums
  * each frame's record sizes with the reference's stored-block rule (0 < comp < raw, else stored) into finfo[f][3];
  * places the frames; writes every header (its checksum byte included), record position, EndMark and checksum
  * position, one lane per frame; moves every payload once, one wave per block; and fills in the block and content
@@ -583,7 +601,7 @@ int32_t lz4mi_frames_compress(const uint8_t* in, const uint64_t* blk_in_off, con
 /*
  * The same two contracts on the calling thread (host pointers, no device needed; flags without
  * LZ4MI_DEVICE_PTRS): the checker of the device passes. The encoder is lz4mi_host_compress_block with a fresh
- * table per block. A `work` that does not hold the slots of the caller's own lists is LZ4MI_ERR_ARG here (the
+ * table per block, or with LZ4MI_FRAMES_CHAINS one table carried across a multi-block dependent frame. A `work` that does not hold the slots of the caller's own lists is LZ4MI_ERR_ARG here (the
  * host sees the lists).
  */
 int32_t lz4mi_host_frames_plan(const uint64_t* src_off, const uint64_t* src_len, uint32_t nframes, uint32_t block_max,
