@@ -177,7 +177,11 @@ const char* lz4mi_build_id(void);
  * a block past them, or a slot that breaks the precondition, is LZ4MI_ERR_ARG for the call with
  * host pointers and status LZ4MI_ERR_ARG for that block (then the after-failure rule) with device
  * pointers -- as is a block of a device-pointer batch whose slots are spread so far that a pass
- * cannot address them (about 1 GiB of `in` or `out` per ~240 blocks of 4 MiB). Valid with
+ * cannot address them. The rule, per pass (at most ~240 blocks of 4 MiB), with in_lo / out_lo the
+ * lowest in_off / out_off of the pass's blocks: block b is refused when
+ *     in_off[b] - in_lo + in_len[b] >= 2^30   or   out_off[b] - out_lo + out_cap[b] + 65536 >= 2^30
+ * (in_len without the stored bit of a frame word; the lowest slot itself counts, so one block
+ * always fits). One byte less in either sum decodes. Valid with
  * LZ4MI_DEVICE_PTRS (asynchronous, nothing read back) and with host pointers (the whole output range
  * is staged: gaps and unused slot tails are history); with LZ4MI_FRAME_WORDS on device pointers a
  * stored block is copied in the same call before anything reads it. Any nblocks: the call cuts the
