@@ -36,23 +36,28 @@
 //     length varints: incompressible or highly repetitive data) is parsed from
 //     global memory with wave-wide 255-run scans. It is written after step 6 by
 //     the whole wave, literal run first, then (after it is stored, and after
-//     step 7) the match run.
+//     step 7) the match run. In the batch kernel a chunk's last sequence that
+//     overruns the window but would fit one it starts is not cut: the chunk ends
+//     at its token and the next chunk begins there (parse_chunk, `defer`).
 //     (Export, XP: the sequences of steps 4 and 5 go to the segment's list
 //     instead, and the chunk ends here.)
 //  6. Output, sequence-parallel (lane l takes sequence 64i+l), every run
 //     written with exact-width unaligned 16/8/4/2/1-byte pieces (the last
 //     16-byte piece of a run overlaps its predecessor instead of spilling),
 //     so lanes never touch each other's bytes:
-//       round 1: all literal runs (from LDS) and every match whose source
-//                lies entirely in output finished by earlier chunks;
+//       round 1: all literal runs (from LDS; those of >= 16 bytes, of any
+//                length, cut into 16-byte pieces that are dealt to the lanes,
+//                64 per store: LitDeal) and every match whose source lies
+//                entirely in output finished by earlier chunks;
 //       round r: after the previous round's stores are complete, every
 //                pending match whose source range meets no pending match.
 //     The earliest pending match is always ready, so the rounds terminate;
 //     on typical data two or three suffice. Matches are read straight from
 //     the output (L2, bypassing L1); an overlapping match (offset < length)
 //     is read through its period: a 16-byte window that wraps is merged from
-//     two loads, periods under 16 bytes are expanded in registers. Runs
-//     longer than kLaneBytes are written by the whole wave.
+//     two loads, periods under 16 bytes are expanded in registers. Matches
+//     (and matches remapped into literal runs) longer than kLaneBytes = 256
+//     bytes are written by the whole wave.
 //  7. Reference mode: the chunk's matches replayed with the reference's tail
 //     rewrite where it would change a byte (f1_table, f1_fixup).
 #include "../../include/lz4mi.h"
@@ -146,7 +151,7 @@ constexpr uint32_t kEnd = 0x40000000u;        // chain ends (last sequence of th
 constexpr uint32_t kStop = 0x40000001u;       // sequence cannot be parsed inside the window
 constexpr int kWaveB = 2;                     // ... (whole-wave runs: streaming copies)
 constexpr int kWaveB2 = 1;                    // ... (whole-wave periodic runs: two windows per piece)
-constexpr int kLaneBytes = 256;               // longer runs are written by the whole wave (128: tiles216 +1.8 %)
+constexpr int kLaneBytes = 256;               // longer match runs are written by the whole wave (128: tiles216 +1.8 %)
 constexpr int kPeriodBulk = 1024;             // longer periodic runs are generated from an LDS copy of the pattern
 constexpr int32_t kLongLit = 4096;            // literal runs at least this long: long_literals()
 constexpr uint64_t kXRatioMax = 32;           // XP: blocks of higher ratio are decoded by one wave
@@ -1007,21 +1012,94 @@ __device__ __forceinline__ void short_literals(const Ctx& c, int32_t y, int32_t 
     if (n & 1) d[o] = (uint8_t)lo;
 }
 
-// Each lane copies its own short literal runs (LDS -> output; no vector-memory loads).
-__device__ __forceinline__ void lane_literals(const Ctx& c, const DecShared& S, const Run& L) {
-    const int32_t n = L.kind == R_NONE ? 0 : L.n;
-    const int np = n >= 16 ? (n + 15) >> 4 : 0;
-    for (int q = 0; __ballot(q < np) != 0; q += 2) {       // runs of >= 16 bytes: 16-byte pieces
-        const int32_t d0 = 16 * q < n - 16 ? 16 * q : n - 16, d1 = 16 * (q + 1) < n - 16 ? 16 * (q + 1) : n - 16;
-        const uint4 v0 = stage16(S.stage, L.src + d0);
-        const uint4 v1 = stage16(S.stage, L.src + d1);
-        if (LZ4MI_ABLATE == 4) continue;
-        if (q < np) out16(c.dst + L.y + d0, v0);
-        if (q + 1 < np) out16(c.dst + L.y + d1, v1);
+// Literal runs of >= 16 bytes from the staged chunk (R_LDS), piece-parallel like the matches of
+// piece_pipe: every run is cut into 16-byte pieces (the last one overlaps its predecessor, so
+// no byte outside [y, y + n) is written) and the pieces of all listed runs are dealt to the
+// lanes in order, 64 per row; a lane does one stage16 and one out16 per row instead of every
+// lane going round as often as the row's longest run needs. The run list (rank -> {y, stage
+// index, n, first piece}) and the first-piece bitmap live in S.pms: the token list there is
+// dead after seq_table, and round 1 needs it only for a whole-wave periodic match
+// (pat_round1), before which the list is flushed.
+// Two users: the chunk's own literal runs, once before round 1's loop (dealt_literals), and
+// round 1's remapped sources (a match mapped into a literal run, the literal prefix of a
+// split match), listed row by row and flushed when the list is full and after the loop.
+// Bounds: the literals of a table's sequences lie inside the window (else the sequence is
+// cut), so a chunk's own runs hold <= kLim bytes together, and each run of >= 16 bytes takes
+// >= 17 compressed bytes of a token starting in the chunk: all of them fit one list. A
+// remapped run is at most kLaneBytes long.
+constexpr int kLitRuns = 64;                                   // list entries
+constexpr int kLitRows = kLitRuns * (kLaneBytes / 16) / 64;    // bitmap rows
+static_assert((kChunk + 16) / 17 <= kLitRuns, "every run of >= 16 literal bytes of a chunk has a list entry");
+static_assert(kLim / 16 + kLitRuns <= 3 * 64, "a chunk's own runs: at most three piece rows");
+static_assert(kLim / 16 + kLitRuns <= kLitRows * 64, "... which the bitmap holds");
+static_assert(kLitRuns * sizeof(PEnt) + kLitRows * 8 <= sizeof(uint32_t) * kMaxSeq, "run list and bitmap fit S.pms");
+static_assert(kLitRows <= kWave, "one lane clears each bitmap word");
+static_assert(offsetof(DecShared, pms) % 16 == 0, "16-byte aligned list entries");
+
+struct LitDeal {
+    uint32_t P = 0, R = 0;   // pieces and runs listed (wave-uniform)
+    static __device__ __forceinline__ PEnt* list(DecShared& S) { return reinterpret_cast<PEnt*>(S.pms); }
+    static __device__ __forceinline__ uint64_t* bitmap(DecShared& S) {
+        return reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(S.pms) + kLitRuns * sizeof(PEnt));
     }
-    if (__ballot(n > 0 && n < 16)) {                       // shorter runs: one stage read
-        if (n > 0 && n < 16) short_literals(c, L.y, n, stage16(S.stage, L.src));
+    // Lists the run {y, src, n >= 16} of every lane with `has` (bal = its ballot, not 0; at most
+    // kLitRuns - R lanes).
+    __device__ __forceinline__ void add(DecShared& S, int lane, bool has, uint64_t bal, int32_t y, int32_t src, int32_t n) {
+        if (R == 0) {
+            if (lane < kLitRows) bitmap(S)[lane] = 0;
+            __syncthreads();
+        }
+        const uint32_t np = has ? (uint32_t)(n + 15) >> 4 : 0u;
+        const uint32_t incl = wave_incl_scan(np, lane);
+        const uint32_t r = R + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        const uint32_t p0 = P + incl - np;
+        if (has) {
+            list(S)[r] = PEnt{y, src, n, (int32_t)p0};
+            atomicOr((unsigned long long*)&bitmap(S)[p0 >> 6], 1ull << (p0 & 63u));
+        }
+        P += lane_of(incl, kWave - 1);
+        R += (uint32_t)__popcll(bal);
     }
+    // Writes the listed runs and empties the list.
+    __device__ __forceinline__ void flush(const Ctx& c, DecShared& S, int lane) {
+        if (R == 0) return;
+        __syncthreads();
+        const PEnt* L = list(S);
+        const uint64_t* bm = bitmap(S);
+        int32_t rb = -1;   // ranks before this row, minus one
+        for (uint32_t t = 0; 64u * t < P; ++t) {
+            const uint64_t w = bm[t];
+            const int32_t below = (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(w >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)w, 0u));
+            const int32_t r = rb + below + (int32_t)((w >> lane) & 1u);
+            rb += __popcll(w);
+            const uint32_t p = 64u * t + (uint32_t)lane;
+            if (p < P) {
+                const PEnt e = L[r];
+                const int32_t d0 = 16 * ((int32_t)p - e.p0);
+                const int32_t d = d0 < e.n - 16 ? d0 : e.n - 16;
+                const uint4 v = stage16(S.stage, e.src + d);
+                if (LZ4MI_ABLATE != 4) out16(c.dst + e.y + d, v);
+            }
+        }
+        __syncthreads();   // the list may be rewritten, or S.pms reused (pat_round1)
+        P = R = 0;
+    }
+};
+
+// The chunk's own literal runs of >= 16 bytes. A chunk without one (text, copy) pays a ballot
+// per sequence row.
+__device__ __forceinline__ void dealt_literals(const Ctx& c, DecShared& S, int lane, uint32_t nseq) {
+    LitDeal D;
+    for (uint32_t i = 0; 64 * i < nseq; ++i) {
+        const uint32_t k = 64 * i + lane;
+        const uint4& e = S.t_seq[k < nseq ? k : 0u];
+        const uint32_t y = e.x, lw = e.y;
+        const uint32_t n = k < nseq ? lw >> 16 : 0u;
+        const bool has = n >= 16;
+        const uint64_t bal = __ballot(has);
+        if (bal) D.add(S, lane, has, bal, (int32_t)y, (int32_t)(lw & 0xFFFFu), (int32_t)n);
+    }
+    D.flush(c, S, lane);
 }
 
 // Wave-wide 255-run varint starting at block-relative q: returns the sum and
@@ -1321,7 +1399,12 @@ struct Parse {
     int last_lane;
     bool cut;
 };
-__device__ __forceinline__ Parse parse_chunk(DecShared& S, int lane, uint32_t rem, bool fast_tab, Prof& prof) {
+// `defer`: a last token whose sequence overruns the window but would fit one it starts (by the
+// fast table's raw next value: under kLim bytes) is left to the next chunk, which begins at it,
+// instead of being cut: its literals then come from LDS and its match joins the piece list
+// (tiles216: 151 cuts in a block's 484 chunks are such sequences of 65-261 literal bytes).
+// The chunk's first token is never deferred, so every chunk advances.
+__device__ __forceinline__ Parse parse_chunk(DecShared& S, int lane, uint32_t rem, bool fast_tab, bool defer, Prof& prof) {
     const uint8_t* s = (const uint8_t*)S.stage;
     const uint32_t seg0 = 16u * lane, seg1 = seg0 + 16;
     uint32_t vis, tail;
@@ -1407,11 +1490,16 @@ __device__ __forceinline__ Parse parse_chunk(DecShared& S, int lane, uint32_t re
     }
     if (nE >= seg1) vis = 0;
     else vis &= ~((1u << (nE - seg0)) - 1u);
-    tail = lane_of(x, kWave - 1);   // where the chain leaves the chunk
+    const uint32_t raw = lane_of(x, kWave - 1);   // where the chain leaves the chunk
+    tail = raw;
     if (tail > (uint32_t)kLim && tail < kEnd) tail = kStop;   // (fast table: raw positions past the window)
     const uint64_t has = __ballot(vis != 0);
     const int last_lane = 63 - __builtin_clzll(has);
     const uint32_t last_tok = lane_val(seg0 + 31 - __builtin_clz(vis | 1u), (uint32_t)last_lane);
+    if (defer && fast_tab && tail == kStop && raw < kEnd && last_tok != 0 && raw - last_tok <= (uint32_t)kLim) {
+        if (lane == last_lane) vis &= ~(1u << (last_tok - seg0));
+        return Parse{vis, last_tok, last_tok, last_lane, false};
+    }
     return Parse{vis, tail, last_tok, last_lane, tail == kStop};
 }
 
@@ -1727,16 +1815,19 @@ __device__ __forceinline__ uint32_t round1(const Ctx& c, DecShared& S, int lane,
     uint32_t ready = 0;   // bit i: ... is written by this lane in this round
     uint32_t rbits = 0;   // bit i: ... reads a remapped source (SeqInfo::rsrc)
     uint32_t nlit_pack = 0;   // byte i (rows < 4): literal prefix of a split match (remap_src 3)
+    dealt_literals(c, S, lane, nseq);
+    LitDeal D;   // the remapped sources' literal runs
     for (uint32_t i = 0; 64 * i < nseq; ++i) {            // round 1
         const uint32_t k = 64 * i + lane;
         Run M = no_run(), ML = no_run();
         SeqInfo q = seq_info(S, k < nseq ? k : 0u);
         if (k >= nseq) q.ll = 0;
         {   // the literal runs first (their registers are free before the remap)
-            const Run L = q.ll ? Run{q.out, q.ll, q.lit, 0, R_LDS} : no_run();
-            const bool longL = L.n > kLaneBytes;
-            lane_literals(c, S, longL ? no_run() : L);
-            for (uint64_t lm = __ballot(longL); lm; lm &= lm - 1) wave_run(c, S, lane, shfl_run(L, __builtin_ctzll(lm)), no_pat());
+            // (runs of >= 16 bytes: dealt_literals, before this loop)
+            const bool shortL = q.ll > 0 && q.ll < 16;
+            if (__ballot(shortL)) {
+                if (shortL) short_literals(c, q.out, q.ll, stage16(S.stage, q.lit));
+            }
         }
         PROF(23);
         if (k < nseq) {
@@ -1776,13 +1867,26 @@ __device__ __forceinline__ uint32_t round1(const Ctx& c, DecShared& S, int lane,
         const bool fastM = M.kind == R_HIST && M.period == 0 && M.n >= 16;
         if (M.kind != R_NONE && !longM && fastM) ready |= 1u << i;
         PROF(16);
-        lane_literals(c, S, longML ? no_run() : ML);
+        {
+            const bool dealML = ML.n >= 16 && !longML, shortML = ML.n > 0 && ML.n < 16;
+            if (const uint64_t bal = __ballot(dealML)) {
+                if (D.R + (uint32_t)__popcll(bal) > (uint32_t)kLitRuns) D.flush(c, S, lane);
+                D.add(S, lane, dealML, bal, ML.y, ML.src, ML.n);
+            }
+            if (__ballot(shortML)) {
+                if (shortML) short_literals(c, ML.y, ML.n, stage16(S.stage, ML.src));
+            }
+        }
         PROF(17);
         for (uint64_t lm = __ballot(longML); lm; lm &= lm - 1) wave_run(c, S, lane, shfl_run(ML, __builtin_ctzll(lm)), no_pat());
         if (M.kind != R_NONE && !longM && !fastM) lane_slow_run(c, S, M);
-        for (uint64_t mm = __ballot(longM); mm; mm &= mm - 1) wave_run(c, S, lane, shfl_run(M, __builtin_ctzll(mm)), pat_round1(S));
+        if (const uint64_t mm0 = __ballot(longM)) {
+            D.flush(c, S, lane);   // (pat_round1 is the list's LDS)
+            for (uint64_t mm = mm0; mm; mm &= mm - 1) wave_run(c, S, lane, shfl_run(M, __builtin_ctzll(mm)), pat_round1(S));
+        }
         PROF(18);
     }
+    D.flush(c, S, lane);
     piece_pipe(c, S, ready, rbits, lane, nseq, nlit_pack);
     return pend;
 }
@@ -1960,7 +2064,7 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
         Parse P;
         SeqTable T;
         for (bool fast_tab = rem > kFastRem;; fast_tab = false) {
-            P = parse_chunk(S, lane, rem, fast_tab, prof);                  // 2, 3
+            P = parse_chunk(S, lane, rem, fast_tab, !XP, prof);             // 2, 3
             // the next chunk's bytes: loaded while this chunk's table is built
             if (LZ4MI_ABLATE != 3 && !P.cut && P.tail < kEnd && (int64_t)c.ip + P.tail < c.in_len)
                 prefetch(c, pf, (int64_t)c.ip + P.tail, lane);

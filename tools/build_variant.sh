@@ -16,7 +16,7 @@ sed -i 's|"../../include/lz4mi.h"|"lz4mi.h"|' $T/*.hip $T/*.cpp $T/*.h   # (the 
 mkdir -p $R/tools/variants
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$R/include $*"
 objs=""
-for f in lz4mi_decompress.hip lz4mi_expand.hip lz4mi_decompress_serial.hip lz4mi_size.hip lz4mi_compress.hip lz4mi_xxh32.hip lz4mi_frame.hip lz4mi_capi.cpp lz4mi_host.cpp; do
+for f in lz4mi_decompress.hip lz4mi_expand.hip lz4mi_decompress_serial.hip lz4mi_size.hip lz4mi_compress.hip lz4mi_xxh32.hip lz4mi_frame.hip lz4mi_frames.hip lz4mi_frames_enc.hip lz4mi_capi.cpp lz4mi_host.cpp; do
   srcf=$T/$f
   /opt/rocm/bin/hipcc $F -c -o $T/$f.o $srcf & objs="$objs $T/$f.o"
 done
