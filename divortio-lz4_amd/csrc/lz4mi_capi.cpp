@@ -1092,11 +1092,22 @@ int32_t lz4mi_frames_decompress(const uint8_t* in, const uint64_t* blk_in_off, c
                                 const uint32_t* blk_frame, const uint32_t* blk_size, uint32_t nblocks, int64_t* finfo,
                                 uint32_t nframes, uint8_t* out, const uint64_t* frame_out_off,
                                 const uint64_t* frame_out_cap, uint32_t flags, void* stream) {
-    if (!(flags & LZ4MI_DEVICE_PTRS) || (flags & ~(LZ4MI_DEVICE_PTRS | LZ4MI_JS_EXACT | LZ4MI_VERIFY_CONTENT)))
+    if (!(flags & LZ4MI_DEVICE_PTRS) ||
+        (flags & ~(LZ4MI_DEVICE_PTRS | LZ4MI_JS_EXACT | LZ4MI_VERIFY_CONTENT | LZ4MI_FRAMES_CHAINS)))
         return LZ4MI_ERR_ARG;
     if ((nframes && (!finfo || !frame_out_off || !frame_out_cap || !out || !in)) ||
         (nblocks && (!blk_in_off || !blk_word || !blk_frame || !blk_size)))
         return LZ4MI_ERR_ARG;
+    // LZ4MI_FRAMES_CHAINS: a chain reads the bytes it wrote, `in` and the lists while finfo and `out` change, so the
+    // arrays the call writes may not be the ones it reads, nor each other (checked for the pointers themselves)
+    if ((flags & LZ4MI_FRAMES_CHAINS) && nframes) {
+        const void* wr[2] = {finfo, out};
+        const void* rd[7] = {in, blk_in_off, blk_word, blk_frame, blk_size, frame_out_off, frame_out_cap};
+        if (wr[0] == wr[1]) return LZ4MI_ERR_ARG;
+        for (const void* w : wr)
+            for (const void* r : rd)
+                if (r && w == r) return LZ4MI_ERR_ARG;
+    }
     DeviceGuard dg;
     if (dg.status()) return dg.status();
     if (nframes == 0) return LZ4MI_OK;
@@ -1121,9 +1132,18 @@ int32_t lz4mi_frames_decompress(const uint8_t* in, const uint64_t* blk_in_off, c
                                         out_off, out_cap, flags, s));
     // the batch kernel (never the small path), frame words, every block isolated -- a lone block too
     const Batch batch{in, blk_in_off, word, out, out_off, out_cap, nullptr, 0, out_len, status, nblocks};
-    LZ4MI_TRY(decode_launch(batch, ((flags & LZ4MI_JS_EXACT) ? 2 : 0) | 4, s, &c->order, nullptr, 0, 0, 1));
-    LZ4MI_TRY(lz4mi_launch_frames_finish(finfo, nframes, nblocks, word, out_off, out_cap, out_len, status, out,
-                                         frame_out_off, hash_off, hash_len, hashed, digest, flags, s));
+    const int mode = (flags & LZ4MI_JS_EXACT) ? 2 : 0;
+    LZ4MI_TRY(decode_launch(batch, mode | 4, s, &c->order, nullptr, 0, 0, 1));
+    // LZ4MI_FRAMES_CHAINS: the place pass left word 0 for the blocks of the multi-block dependent frames; one wave
+    // per frame decodes those in order, and any other frame from its first LZ4MI_ERR_CROSS_BLOCK on, over the real
+    // size words, which the finish pass then reads too
+    const bool chains = (flags & LZ4MI_FRAMES_CHAINS) != 0;
+    if (chains) {
+        const Batch real{in, blk_in_off, blk_word, out, out_off, out_cap, nullptr, 0, out_len, status, nblocks};
+        LZ4MI_TRY(lz4mi_launch_decompress_frames_chain(real, mode, finfo, frame_out_off, nframes, s));
+    }
+    LZ4MI_TRY(lz4mi_launch_frames_finish(finfo, nframes, nblocks, chains ? blk_word : word, out_off, out_cap, out_len,
+                                         status, out, frame_out_off, hash_off, hash_len, hashed, digest, flags, s));
     return LZ4MI_OK;
 }
 

@@ -1234,7 +1234,7 @@ __device__ __noinline__ void f1_fixup(const Ctx c, const DecShared& S, int lane,
 // ---------------------------------------------------------------- the block
 // A frame's stored block (bufferDecompress.js:173-180): its bytes, in this launch, paced
 // like any long literal run; larger than the slot: the reference's RangeError.
-__device__ __forceinline__ void stored_block(const DecArgs& a, const Ctx& c, uint32_t b, uint32_t out_cap, int lane) {
+__device__ __forceinline__ int32_t stored_block(const DecArgs& a, const Ctx& c, uint32_t b, uint32_t out_cap, int lane) {
     int32_t status = 0;
     const int32_t n = c.in_len;
     if ((uint32_t)n > out_cap) {
@@ -1248,6 +1248,7 @@ __device__ __forceinline__ void stored_block(const DecArgs& a, const Ctx& c, uin
         a.status[b] = status;
         a.out_len[b] = status ? 0u : (uint32_t)n;
     }
+    return status;
 }
 
 // ---------------------------------------------------------------- export (XP)
@@ -2004,17 +2005,22 @@ constexpr bool kOutput = LZ4MI_ABLATE == 0 || LZ4MI_ABLATE >= 4;      // (else t
 constexpr bool kParseOnly = LZ4MI_ABLATE == 2 || LZ4MI_ABLATE == 3;   // (timing only: steps 1-3)
 
 // XP: the small-batch export, a wave per segment of the block (x_enter); LK: a linked window.
-template <bool XP, bool LK = false>
-__device__ __forceinline__ void decompress_block(const DecArgs& a) {
+// CH: the caller names the block (cblk, instead of blockIdx.x and the order / redo lists) and the array it is a
+// block of, which begins at out + cbase: Ctx::out_off is the slot's position in that array (the chains of a frame
+// batch, lz4mi_decompress_frames_chain_kernel). Returns the status written to status[b] (0 where none is). The
+// three batch kernels take none of this: with CH = false the function compiles to what it was without it -- a
+// split into a wrapper and a per-block function did not (other register allocation, bench.py 0.7 % slower).
+template <bool XP, bool LK = false, bool CH = false>
+__device__ __forceinline__ int32_t decompress_block(const DecArgs& a, uint32_t cblk = 0, uint64_t cbase = 0) {
     __shared__ DecShared S;
     const int lane = threadIdx.x;
     const uint32_t nseg = XP ? a.xsegs : 1u;   // XP: waves per block (one per segment)
-    if (blockIdx.x >= a.nblocks * nseg) return;
-    const uint32_t wblk = XP ? blockIdx.x / nseg : blockIdx.x;   // (XP: block-major, segments of a block on
+    if (!CH && blockIdx.x >= a.nblocks * nseg) return 0;
+    const uint32_t wblk = CH ? cblk : XP ? blockIdx.x / nseg : blockIdx.x;   // (XP: block-major, segments of a block on
     const uint32_t sg = XP ? blockIdx.x - wblk * nseg : 0u;       //  consecutive CUs, every XCD)
-    if (LK && uniform(a.xcnt[wblk]) == kNotExported) return;     // stored, refused or after a failure: not parsed
-    const uint32_t b = a.order ? uniform(a.order[wblk]) : wblk;
-    if (!XP && a.redo && !uniform(a.redo[b])) return;   // (small batches, reference mode: the blocks to redo)
+    if (LK && uniform(a.xcnt[wblk]) == kNotExported) return 0;     // stored, refused or after a failure: not parsed
+    const uint32_t b = CH ? cblk : a.order ? uniform(a.order[wblk]) : wblk;
+    if (!CH && !XP && a.redo && !uniform(a.redo[b])) return 0;   // (small batches, reference mode: the blocks to redo)
 #if LZ4MI_TIMELINE
     const uint64_t tl_t0 = wall_clock64();
 #endif
@@ -2026,7 +2032,7 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
     c.blk = a.in + in_off;
     const uint32_t word = uniform(a.in_len[b]);
     c.in_len = (int32_t)(a.frame_words ? word & 0x7FFFFFFFu : word);
-    c.out_off = (int64_t)out_off;
+    c.out_off = CH ? (int64_t)(out_off - cbase) : (int64_t)out_off;
     c.dst = a.out + out_off;
     c.cap = out_cap > 0x7FFFFFFFu ? 0x7FFFFFFF : (int32_t)out_cap;
     c.dict = a.dict;
@@ -2035,12 +2041,11 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
     c.ip = 0;
     c.O = 0;
     if (a.frame_words && (word & 0x80000000u)) {
-        stored_block(a, c, b, out_cap, lane);
-        return;
+        return stored_block(a, c, b, out_cap, lane);
     }
     XState x;   // (XP)
     if constexpr (XP) {
-        if (!x_enter<LK>(a, c, x, lane, wblk, sg, nseg, out_cap)) return;
+        if (!x_enter<LK>(a, c, x, lane, wblk, sg, nseg, out_cap)) return 0;
     }
     const bool xp = XP && x.on;   // parsed for export; else decoded here
 #if LZ4MI_LL_ADAPT
@@ -2181,7 +2186,7 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
 #if LZ4MI_LL_ADAPT
             if (lat_bound && lane == 0) atomicSub(lat, 1u);
 #endif
-            return;   // status and length: lz4mi_xcheck_kernel
+            return 0;   // status and length: lz4mi_xcheck_kernel
         }
     }
 #if LZ4MI_PROFILE
@@ -2209,13 +2214,14 @@ __device__ __forceinline__ void decompress_block(const DecArgs& a) {
         g_tl_id[2 * b + 1] = xcc;
     }
 #endif
+    return status;
 }
 
-__global__ __launch_bounds__(64, 4) void lz4mi_decompress_kernel(DecArgs a) { decompress_block<false>(a); }
+__global__ __launch_bounds__(64, 4) void lz4mi_decompress_kernel(DecArgs a) { (void)decompress_block<false>(a); }
 // small batches: a wave per segment of each block, sequences exported (lz4mi_expand.hip)
-__global__ __launch_bounds__(64, 4) void lz4mi_decompress_x_kernel(DecArgs a) { decompress_block<true>(a); }
+__global__ __launch_bounds__(64, 4) void lz4mi_decompress_x_kernel(DecArgs a) { (void)decompress_block<true>(a); }
 // a linked window: every parsed block exported (no one-wave shortcuts)
-__global__ __launch_bounds__(64, 4) void lz4mi_decompress_xl_kernel(DecArgs a) { decompress_block<true, true>(a); }
+__global__ __launch_bounds__(64, 4) void lz4mi_decompress_xl_kernel(DecArgs a) { (void)decompress_block<true, true>(a); }
 
 // After phase 0 and after phase 2 of an exported small batch, per block: the segments in order
 // from segment 0 (whose entry is the block's first token): each whose speculative entry equals
@@ -2386,6 +2392,54 @@ __global__ __launch_bounds__(1024) void lz4mi_block_order_kernel(const uint32_t*
     for (uint32_t i = t; i < n; i += 1024) order[i] = (uint32_t)key[i];
 }
 
+// (Defined behind every other kernel of the file: theirs stay where they were in the code object.)
+// The decode twin of lz4mi_compress_chains_kernel (LZ4MI_FRAMES_CHAINS, lz4mi_frames.hip): one wave per frame of a
+// frame batch, behind the place pass and the isolated batch launch. A chain frame (FLG without 0x20, more than
+// one block: the place pass gave the isolated launch word 0 for its blocks) is decoded from block 0; any other
+// frame from its first block whose isolated status is LZ4MI_ERR_CROSS_BLOCK, if it has one. From there on, in
+// block order, every block is decoded as a lone block (isolate 0) of an array that begins at the frame's slot:
+// Ctx::out_off is the slot-relative position, so nothing below the frame's first byte is read or written. The
+// block before is history once its stores are complete (wait_vmem), as a chunk's predecessor is. After the
+// first failing block the later ones get LZ4MI_ERR_CROSS_BLOCK and out_len 0 and are not written
+// (LZ4MI_LINKED's rule, per frame). `a`: the lists with the real size words, isolate 0, no dictionary.
+__global__ __launch_bounds__(64, 4) void lz4mi_decompress_frames_chain_kernel(DecArgs a, const int64_t* finfo,
+                                                                              const uint64_t* frame_out_off,
+                                                                              uint32_t nframes) {
+    const int lane = threadIdx.x;
+    const uint32_t f = blockIdx.x;
+    if (f >= nframes) return;
+    const int64_t* fi = finfo + 8ull * f;
+    if (uniform64((uint64_t)fi[0]) || uniform64((uint64_t)fi[7])) return;   // in error or declined
+    const uint64_t first = uniform64((uint64_t)fi[4]), n = uniform64((uint64_t)fi[6]);
+    if (first > a.nblocks || n > a.nblocks - first) return;                 // its blocks are outside the lists
+    const uint64_t base = uniform64(frame_out_off[f]);
+    uint64_t k = 0;
+    if ((uniform64((uint64_t)fi[1]) & 0x20) || n < 2) {   // not a chain frame: was a block left to the chain?
+        uint64_t hit = 0;
+        for (; k < n && !hit; k += kWave) {
+            const uint64_t q = k + lane;
+            hit = __ballot(q < n && a.status[first + q] == LZ4MI_ERR_CROSS_BLOCK);
+        }
+        if (!hit) return;
+        k = k - kWave + (uint64_t)__builtin_ctzll(hit);
+    }
+    bool failed = false;
+    for (; k < n; ++k) {
+        const uint32_t b = (uint32_t)(first + k);
+        if (failed) {
+            if (lane == 0) {
+                a.status[b] = LZ4MI_ERR_CROSS_BLOCK;
+                a.out_len[b] = 0;
+            }
+            continue;
+        }
+        failed = uniform((uint32_t)decompress_block<false, false, true>(a, b, base)) != 0;
+        // the block's bytes are the next one's history, and DecShared is free again
+        wait_vmem();
+        __syncthreads();
+    }
+}
+
 }  // namespace lz4mi
 
 #if LZ4MI_PROFILE
@@ -2436,6 +2490,21 @@ extern "C" hipError_t lz4mi_launch_decompress(const Batch& b, int mode, int isol
         a.order = order;
     }
     hipLaunchKernelGGL(lz4mi::lz4mi_decompress_kernel, dim3(nblocks), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+// The chains of a frame batch (lz4mi_decompress_frames_chain_kernel): b.in_len holds the frames' real size
+// words, b.status / b.out_len what the isolated launch left. mode: 0 or 2, as above.
+extern "C" hipError_t lz4mi_launch_decompress_frames_chain(const Batch& b, int mode, const int64_t* finfo,
+                                                           const uint64_t* frame_out_off, uint32_t nframes,
+                                                           hipStream_t stream) {
+    if (nframes == 0 || b.nblocks == 0) return hipSuccess;
+    DecArgs a = dec_args(b, 0, mode == 2 ? 1 : 0);
+    a.dict = nullptr;
+    a.dict_len = 0;
+    a.frame_words = 1;
+    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_frames_chain_kernel, dim3(nframes), dim3(64), 0, stream, a, finfo,
+                       frame_out_off, nframes);
     return hipGetLastError();
 }
 

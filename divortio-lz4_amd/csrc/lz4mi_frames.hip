@@ -10,6 +10,10 @@
 //   decompress: place (lane per frame: out_off / out_cap / the words the decoder sees) -> the batch
 //               decode kernel -> finish (wave per frame: the frame's status, zero tail, hash list) ->
 //               lz4mi_launch_xxh32 -> compare (lane per frame)
+//               with LZ4MI_FRAMES_CHAINS the chain kernel (lz4mi_decompress.hip, wave per frame) runs between
+//               the batch kernel and the finish: the place pass hides the blocks of the multi-block dependent
+//               frames from the batch kernel (word 0), the chain decodes them in order, and with them every
+//               other frame from its first block that reached below its own start
 // The per-frame steps of the index are lz4mi_frames.h, shared with lz4mi_host_frames_index.
 #include "lz4mi_common.h"
 #include "lz4mi_frames.h"
@@ -105,8 +109,14 @@ __device__ __forceinline__ bool active(const int64_t* fi, uint32_t nblocks) {
     return first <= nblocks && n <= nblocks - first;
 }
 
+// Is frame fi one whose blocks the chain kernel decodes from block 0 (LZ4MI_FRAMES_CHAINS)? The test of
+// lz4mi_decompress_frames_chain_kernel.
+__device__ __forceinline__ bool chain_frame(const int64_t* fi) { return !(fi[kHead] & 0x20) && fi[kCount] > 1; }
+
 // Place pass. The caller has zeroed word / out_off / out_cap for all nblocks: a block of a frame that is
-// not decoded stays a no-op (word 0, capacity 0: nothing is read or written for it).
+// not decoded stays a no-op (word 0, capacity 0: nothing is read or written for it). With LZ4MI_FRAMES_CHAINS
+// the blocks of a chain frame keep word 0 (the batch kernel passes them over; the chain kernel and the finish
+// pass read blk_word) and get their slots.
 __global__ __launch_bounds__(64) void lz4mi_frames_place_kernel(int64_t* finfo, uint32_t nframes,
                                                                 const uint32_t* blk_word, const uint32_t* blk_size,
                                                                 uint32_t nblocks, const uint64_t* frame_out_off,
@@ -137,10 +147,11 @@ __global__ __launch_bounds__(64) void lz4mi_frames_place_kernel(int64_t* finfo, 
         return;
     }
     const uint64_t first = (uint64_t)fi[kFirst], n = (uint64_t)fi[kCount], base = frame_out_off[f];
+    const bool chained = (flags & LZ4MI_FRAMES_CHAINS) && chain_frame(fi);
     uint64_t run = 0;
     for (uint64_t b = first; b < first + n; ++b) {
         const uint64_t sz = blk_size[b], left = total - run;
-        word[b] = blk_word[b];
+        word[b] = chained ? 0u : blk_word[b];
         out_off[b] = base + run;
         out_cap[b] = (uint32_t)(sz < left ? sz : left);   // never past the frame's total: a stored block that
         run += sz < left ? sz : left;                     // does not fit is the decoder's LZ4MI_ERR_RANGE
@@ -161,7 +172,10 @@ __device__ __forceinline__ void wave_zero(uint8_t* dst, uint64_t n, int lane) {
     }
 }
 
-// Finish pass: one wave per frame over its blocks' statuses and lengths, in block order.
+// Finish pass: one wave per frame over its blocks' statuses and lengths, in block order. With
+// LZ4MI_FRAMES_CHAINS (`word` is then blk_word) only the blocks up to and including the first failing one decide
+// whether the frame is declined: behind it the chain left LZ4MI_ERR_CROSS_BLOCK and length 0 (the after-failure
+// rule), which are no findings about the frame.
 __global__ __launch_bounds__(64) void lz4mi_frames_finish_kernel(int64_t* finfo, uint32_t nframes, uint32_t nblocks,
                                                                  const uint32_t* word, const uint64_t* out_off,
                                                                  const uint32_t* out_cap, const uint32_t* out_len,
@@ -181,7 +195,7 @@ __global__ __launch_bounds__(64) void lz4mi_frames_finish_kernel(int64_t* finfo,
     const uint64_t first = (uint64_t)fi[kFirst], n = (uint64_t)fi[kCount], base = frame_out_off[f];
     const uint64_t size = (uint64_t)fi[kSize], total = (uint64_t)fi[kTotal];
     const bool measured = (fi[kHead] & kMeasured) != 0, has_size = sized(fi);
-    const bool exact = (flags & LZ4MI_JS_EXACT) != 0;
+    const bool exact = (flags & LZ4MI_JS_EXACT) != 0, chains = (flags & LZ4MI_FRAMES_CHAINS) != 0;
     int32_t first_st = 0;
     bool dependent = false, layout = false;
     uint64_t written = 0;
@@ -190,6 +204,11 @@ __global__ __launch_bounds__(64) void lz4mi_frames_finish_kernel(int64_t* finfo,
         const bool valid = k < n;
         const uint64_t b = first + (valid ? k : 0);
         int32_t st = valid ? status[b] : 0;
+        bool decides = valid;   // does the block count for the declines?
+        if (chains) {
+            const uint64_t bad = __ballot(valid && st != 0);
+            decides = valid && !first_st && (!bad || lane <= __builtin_ctzll(bad));
+        }
         const uint32_t ol = out_len[b], cap = out_cap[b], w = word[b];
         const uint64_t rel = out_off[b] - base;
         const bool stored = (w & 0x80000000u) != 0;
@@ -197,12 +216,12 @@ __global__ __launch_bounds__(64) void lz4mi_frames_finish_kernel(int64_t* finfo,
         // frame's block 0 below the frame's start -- no dictionary, the result starts at position 0: the
         // reference's check 4. In a reference mode block 0 may also report its tail rewrite reading below the
         // frame (f1_changes): that frame is decoded alone.
-        bool dep = valid && st == LZ4MI_ERR_CROSS_BLOCK && (k > 0 || exact);
-        if (valid && st == LZ4MI_ERR_CROSS_BLOCK && !dep) st = LZ4MI_ERR_DICT_OOB;
+        bool dep = decides && st == LZ4MI_ERR_CROSS_BLOCK && (k > 0 || exact);
+        if (decides && st == LZ4MI_ERR_CROSS_BLOCK && !dep) st = LZ4MI_ERR_DICT_OOB;
         bool lay;
-        if (measured) lay = valid && !dep && (st != 0 || ol != cap);   // the single-frame route's host cases
-        else lay = valid && !stored && ((st == 0 && ol != cap && k != n - 1) ||
-                                        (st == LZ4MI_ERR_OUTPUT_TOO_SMALL && rel + cap < size));
+        if (measured) lay = decides && !dep && (st != 0 || ol != cap);   // the single-frame route's host cases
+        else lay = decides && !stored && ((st == 0 && ol != cap && k != n - 1) ||
+                                          (st == LZ4MI_ERR_OUTPUT_TOO_SMALL && rel + cap < size));
         dependent |= __ballot(dep) != 0;
         layout |= __ballot(lay) != 0;
         const uint64_t fail = __ballot(valid && st != 0);

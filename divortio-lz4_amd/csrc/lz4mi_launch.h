@@ -78,6 +78,12 @@ extern "C" {
 // ---- decoder (lz4mi_decompress.hip, lz4mi_decompress_serial.hip, lz4mi_expand.hip, lz4mi_size.hip)
 // isolate: a back-reference below a block's own start is LZ4MI_ERR_CROSS_BLOCK, not followed
 hipError_t lz4mi_launch_decompress(const lz4mi::Batch& b, int mode, int isolate, uint32_t* order, hipStream_t stream);
+// the chains of a frame batch (LZ4MI_FRAMES_CHAINS), behind lz4mi_launch_frames_place and the isolated batch launch:
+// one wave per frame decodes, in block order and with lone-block semantics in an array that begins at the frame's
+// slot, the blocks of a multi-block dependent frame, or of any other frame from its first block with status
+// LZ4MI_ERR_CROSS_BLOCK on; every other frame's wave returns at once. b.in_len: the real size words (blk_word)
+hipError_t lz4mi_launch_decompress_frames_chain(const lz4mi::Batch& b, int mode, const int64_t* finfo,
+                                                const uint64_t* frame_out_off, uint32_t nframes, hipStream_t stream);
 hipError_t lz4mi_launch_decompress_serial(const lz4mi::DecArgs& a, hipStream_t stream);
 size_t lz4mi_small_scratch_bytes(uint32_t nblocks, uint32_t x_in_max, uint32_t x_out_max);
 hipError_t lz4mi_launch_decompress_small(const lz4mi::Batch& b, uint32_t x_in_max, uint32_t x_out_max, void* xs,

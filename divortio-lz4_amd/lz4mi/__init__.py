@@ -640,14 +640,16 @@ def frames_index_dev(in_ptr, frame_off_ptr, frame_len_ptr, nframes, blk_in_off_p
 
 def frames_decompress_dev(in_ptr, blk_in_off_ptr, blk_word_ptr, blk_frame_ptr, blk_size_ptr, nblocks, finfo_ptr,
                           nframes, out_ptr, frame_out_off_ptr, frame_out_cap_ptr, stream=0, js_exact=False,
-                          verify_content=False):
+                          verify_content=False, chains=False):
     """Decode the frames lz4mi_frames_index listed, in one call (include/lz4mi.h lz4mi_frames_decompress): device
     pointers, asynchronous on `stream`; finfo holds each frame's status, bytes written and decline code afterwards.
-    verify_content: LZ4MI_VERIFY_CONTENT, the content checksums on the device."""
+    verify_content: LZ4MI_VERIFY_CONTENT, the content checksums on the device. chains: LZ4MI_FRAMES_CHAINS, frames
+    with dependent blocks are decoded in the call too, one wave per frame in block order."""
     _check(lib().lz4mi_frames_decompress(in_ptr, blk_in_off_ptr, blk_word_ptr, blk_frame_ptr, blk_size_ptr, nblocks,
                                          finfo_ptr, nframes, out_ptr, frame_out_off_ptr, frame_out_cap_ptr,
                                          DEVICE_PTRS | (JS_EXACT if js_exact else 0) |
-                                         (VERIFY_CONTENT if verify_content else 0), stream or None))
+                                         (VERIFY_CONTENT if verify_content else 0) |
+                                         (FRAMES_CHAINS if chains else 0), stream or None))
 
 
 def frames_plan_dev(src_off_ptr, src_len_ptr, nframes, block_max, blk_in_off_ptr, blk_len_ptr, blk_frame_ptr,

@@ -1138,7 +1138,7 @@ def decompress_frame_host(frame, js_exact=False, verify_checksum=True, verify_bl
 
 
 def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measure=False, stream=None, report=None,
-                             return_errors=False, offsets=None, lengths=None, cap_blocks=None):
+                             return_errors=False, offsets=None, lengths=None, cap_blocks=None, chains=False):
     """Decode a batch of device-resident frames with one index call, one output allocation and one decode
     call (lz4mi_frames_index / lz4mi_frames_decompress): the frames' size words are walked in parallel, one
     lane per frame, the blocks of all frames decoded by one batch launch, and with verify_checksum the
@@ -1149,6 +1149,10 @@ def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measu
     a device copy of all input that doubles its memory for the call: frames that already lie in one tensor
     should be passed with offsets and lengths. measure: LZ4MI_FRAMES_MEASURE, every
     frame's block sizes are measured (frames with a content size and partial blocks in the middle).
+    chains: LZ4MI_FRAMES_CHAINS, a frame whose blocks read the blocks before them (what the reference writes
+    by default for anything longer than one block; with js_exact also an independent frame whose tail rewrite
+    reads below a block) is decoded in the same call, one wave per frame in block order, instead of being
+    declined: right for many frames, slow for a few long ones (one wave walks the whole frame).
     Two host synchronisations: finfo and totals read back after the index (a third when cap_blocks -- the
     guess of _decode_measured, or the caller's -- was too small and the index runs again with the exact
     need), and finfo after the decode. A frame the batch declines (finfo[f][7], include/lz4mi.h
@@ -1219,7 +1223,7 @@ def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measu
         lz4mi.frames_decompress_dev(arena.data_ptr(), blk_in_off.data_ptr(), blk32[0].data_ptr(), blk32[1].data_ptr(),
                                     blk32[2].data_ptr(), listed, fin.data_ptr(), nf, out.data_ptr(), slots[0].data_ptr(),
                                     slots[1].data_ptr(), s.cuda_stream, js_exact=js_exact,
-                                    verify_content=verify_checksum)
+                                    verify_content=verify_checksum, chains=chains)
         done = fin[:8 * nf].cpu().numpy().reshape(nf, 8)
     res = [None] * nf
     for f in range(nf):

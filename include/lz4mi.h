@@ -97,7 +97,10 @@ extern "C" {
 #define LZ4MI_FRAMES_PACKED 0x8000u           /* lz4mi_frames_compress: the frames back to back from out[0] */
 #define LZ4MI_FRAMES_CHAINS 0x10000u          /* with LZ4MI_FRAMES_DEPENDENT (alone: LZ4MI_ERR_ARG): a frame of more than
                                                  one block is listed and written too, its blocks encoded in order with
-                                                 one table carried across them, one chain per frame, all chains at once */
+                                                 one table carried across them, one chain per frame, all chains at once.
+                                                 lz4mi_frames_decompress: frames whose blocks read the blocks before
+                                                 them are decoded in the call, one wave per frame in block order,
+                                                 instead of being declined (contract there) */
 
 /* ---- why lz4mi_frames_index / lz4mi_frames_decompress (and lz4mi_frames_plan / lz4mi_frames_compress) leave a
  *      frame to the caller (finfo[f][7]) ---- */
@@ -488,16 +491,36 @@ int32_t lz4mi_frame_index(const uint8_t* frame, uint64_t len, uint64_t* pay_off,
  *       status 0 -- lz4mi_frame_decompress's info[3], with one difference: a stored block that fails
  *       LZ4MI_ERR_RANGE counts nothing here, because it writes nothing (there its bytes are copied clipped at the
  *       content size and counted up to it);
- *   [7] may have become OUT_CAP, LAYOUT, DEPENDENT, HASH_4G, UNSIZED_EXACT (LZ4MI_JS_EXACT given to this call
+ *   [7] may have become OUT_CAP, LAYOUT, DEPENDENT (never with LZ4MI_FRAMES_CHAINS), HASH_4G, UNSIZED_EXACT (LZ4MI_JS_EXACT given to this call
  *       only: a frame without a content size is declined here as the index call would have) or CAP_BLOCKS (finfo
  *       does not fit nblocks).
  * A frame with status 0 and a content size holds content-size bytes, zeros behind what its blocks wrote (the
  * reference's zero-initialised result). Every block is decoded isolated: no frame reads or writes another
  * frame's bytes, a lone block included.
- * flags: LZ4MI_DEVICE_PTRS | LZ4MI_JS_EXACT (the reference decoder's bytes) | LZ4MI_VERIFY_CONTENT. Any other
- * flag or a NULL required pointer: LZ4MI_ERR_ARG before the device is looked at. LZ4MI_LINKED* and
+ * LZ4MI_FRAMES_CHAINS: behind the isolated launch one wave per frame decodes, in block order, (a) every block of a
+ * frame with FLG without 0x20 and more than one block (the isolated launch passes these frames over), and (b) of
+ * any other frame the blocks from its first one with LZ4MI_ERR_CROSS_BLOCK on -- with LZ4MI_JS_EXACT an
+ * independent frame whose tail rewrite reads below a block, a frame flagged independent that is not, block 0
+ * reaching below the frame; the blocks before it are final. Each of these blocks is decoded as a lone block (the
+ * contract of LZ4MI_LINKED / LZ4MI_LINKED_EXACT: successive one-block calls in index order) of an array that begins
+ * at the frame's slot, like the reference's result: a back-reference below the frame's first byte is
+ * LZ4MI_ERR_DICT_OOB, and the reference's tail rewrite below position 0 is not written and reads 0 -- no byte of
+ * another frame or of the caller's below the slot is read or written. After the first failing block of a frame
+ * that block keeps its status and the chain writes nothing of the later ones (LZ4MI_LINKED's after-failure rule,
+ * per frame); [0] is that block's error, only the blocks up to and including it decide a decline, [3] counts the
+ * blocks with status 0 as without the flag, and such a frame is never declined as DEPENDENT. Every other decline
+ * and LZ4MI_VERIFY_CONTENT keep their meaning. Footprint: as below. Cost: a frame's chain is one wave from its
+ * first chained block to its last, so the longest frame is the call's floor (the blocks of a 16 MiB frame are
+ * walked by one wave): the flag pays with many frames, not with a few long ones. Without the flag the call is
+ * what it was, launch for launch.
+ * flags: LZ4MI_DEVICE_PTRS | LZ4MI_JS_EXACT (the reference decoder's bytes) | LZ4MI_VERIFY_CONTENT |
+ * LZ4MI_FRAMES_CHAINS. Any other
+ * flag or a NULL required pointer: LZ4MI_ERR_ARG before the device is looked at; with LZ4MI_FRAMES_CHAINS also a
+ * finfo or `out` that is `in`, one of the lists, frame_out_off, frame_out_cap or the other of the two (the call
+ * reads those while it writes these). LZ4MI_LINKED* and
  * LZ4MI_VERIFY_BLOCKS are not taken: a linked pass has no barrier at a frame's first slot, and the verify kernel
- * takes a single in_total; frames with dependent blocks are declined, block checksums are skipped.
+ * takes a single in_total; block checksums are skipped, and without LZ4MI_FRAMES_CHAINS frames with blocks that
+ * read the blocks before them are declined (DEPENDENT).
  * Footprint: finfo; of `out`, only bytes inside out[frame_out_off[f] .. +finfo[f][3]) of frames that were
  * decoded, failed in a block, or were declined as LAYOUT / DEPENDENT (whose bytes there are unspecified). A
  * frame in error or declined before the decode (every other code) has no byte of `out` written. `in` and the
