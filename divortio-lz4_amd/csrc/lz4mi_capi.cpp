@@ -568,8 +568,9 @@ int32_t lz4mi_decompress_blocks(const uint8_t* in, const uint64_t* in_off, const
         lo = std::min<uint64_t>(lo, out_off[b]);
         hi = std::max<uint64_t>(hi, out_off[b] + out_cap[b]);
     }
-    // (LZ4MI_LINKED_EXACT: a rewrite up to 4 bytes below the first block reads up to 65535 bytes below itself)
-    uint64_t hist = std::min<uint64_t>(lo, lx ? 65536 + 8 : 65536);
+    // (the reference modes: a rewrite up to 4 bytes below the first block reads up to 65535 bytes below itself)
+    const bool rewrites = lx || (flags & (LZ4MI_JS_COMPAT | LZ4MI_JS_EXACT)) != 0;
+    uint64_t hist = std::min<uint64_t>(lo, rewrites ? 65536 + 8 : 65536);
     uint64_t base = lo - hist, img = hi - base;
     lz4mi_advise_output(out + lo, hi - lo);
     std::vector<uint64_t> d_out_off(nblocks);

@@ -521,6 +521,14 @@ int32_t lz4mi_frame_index(const uint8_t* frame, uint64_t len, uint64_t* pay_off,
  * LZ4MI_VERIFY_BLOCKS are not taken: a linked pass has no barrier at a frame's first slot, and the verify kernel
  * takes a single in_total; block checksums are skipped, and without LZ4MI_FRAMES_CHAINS frames with blocks that
  * read the blocks before them are declined (DEPENDENT).
+ * A block ends where its size word says: the bytes behind it read as 0, in the index call's measuring and in the
+ * decode (the rule of lz4mi_decoded_sizes and lz4mi_decompress_blocks), with or without LZ4MI_FRAMES_CHAINS. The
+ * reference reads on in the frame: a cut block whose last offset or length field runs past its end is decoded there
+ * with the bytes that follow it (the next size word), here with zeros in their place. Such a frame is not declined
+ * and its status is the blocks' (0 where the reference has 0), but its bytes and measured sizes may differ from the
+ * reference's; they are equal where the bytes behind the block are 0, as before the EndMark. The caller who must
+ * have the reference's bytes for damaged frames asks lz4mi_host_block_read_end per block (a result above the
+ * block's end) and decodes such a frame alone, as lz4mi.frame.decompress_frame_device does through its host route.
  * Footprint: finfo; of `out`, only bytes inside out[frame_out_off[f] .. +finfo[f][3]) of frames that were
  * decoded, failed in a block, or were declined as LAYOUT / DEPENDENT (whose bytes there are unspecified). A
  * frame in error or declined before the decode (every other code) has no byte of `out` written. `in` and the

@@ -32,10 +32,10 @@ class Run:
     pass
 
 
-def run(packed, fill, exact, verify, chains=True, cap=None, roomless=()):
+def run(packed, fill, exact, verify, chains=True, cap=None, roomless=(), measure=False):
     """Index and decode of the frames in `packed` (arena, offsets, lengths). `out` begins FP.MARGIN bytes into a
     buffer of `fill` bytes; the slots are packed from frame_out_off 0 at 16-byte-aligned offsets, GUARD bytes
-    between two. roomless: frames that get no room (capacity 0)."""
+    between two. roomless: frames that get no room (capacity 0). measure: LZ4MI_FRAMES_MEASURE for the index."""
     from lz4mi.frame import content_size_bound
     t = torch_()
     a, off, ln = packed
@@ -47,7 +47,7 @@ def run(packed, fill, exact, verify, chains=True, cap=None, roomless=()):
     fin = t.zeros(8 * nf + 4, dtype=t.int64, device="cuda")
     lz4mi.frames_index_dev(arena.data_ptr(), d_off.data_ptr(), d_ln.data_ptr(), nf, blk_off.data_ptr(),
                            blk32[0].data_ptr(), blk32[1].data_ptr(), blk32[2].data_ptr(), cap, fin.data_ptr(),
-                           fin.data_ptr() + 64 * nf, js_exact=exact)
+                           fin.data_ptr() + 64 * nf, js_exact=exact, measure=measure)
     h = fin.cpu().numpy()
     r = Run()
     r.exact = exact

@@ -96,9 +96,16 @@ def first_far_reference(comp):
 
 
 class Maker:
-    def __init__(self, seed):
+    """base: the block's position in its frame (tests/chain_blocks_common.py): an explicit offset may
+    reach below the block, and a drawn one is drawn a second time, from a generator of its own, over
+    the history from the frame's start -- the first draw keeps the stream of lengths and literals,
+    so the block's shape, that of base 0."""
+
+    def __init__(self, seed, base=0):
         self.rng = np.random.default_rng(seed)
         self.pos = 0
+        self.base = base
+        self.far = np.random.default_rng([seed, base])
 
     def lits(self, n):
         return bytes(self.rng.integers(0, 256, n, dtype=np.uint8))
@@ -107,7 +114,11 @@ class Maker:
         """One sequence of ll literals and a match of ml bytes at a valid offset (or `off`)."""
         self.pos += ll
         if off is None:
-            off = int(self.rng.integers(1, min(self.pos, 65535) + 1))
+            assert self.pos or self.base, "a match at the first byte of the first block"
+            if self.pos:
+                off = int(self.rng.integers(1, min(self.pos, 65535) + 1))
+            if self.base:
+                off = int(self.far.integers(1, min(self.base + self.pos, 65535) + 1))
         self.pos += ml
         return (self.lits(ll), off, ml)
 
@@ -116,61 +127,61 @@ class Maker:
         return [self.seq(1, int(self.rng.integers(4, 19)) if ml is None else ml) for _ in range(n)]
 
 
-def case_dense():
+def case_dense(base=0):
     """Three-byte sequences (no literals, match length 4-18): 5-6 tokens per 16-byte segment and
     the most tokens a chunk can hold, over six rows."""
-    m = Maker(1)
+    m = Maker(1, base)
     seqs = [m.seq(1, 8)] + [m.seq(0, int(m.rng.integers(4, 19))) for _ in range(700)]
     return seqs, m.lits(9)
 
 
-def cases_rows():
+def cases_rows(base=0):
     """First chunks of exactly n sequences: n - 1 four-byte ones and a literal run that carries the
     parse past the chunk's end (inside the window: the block is short enough for the exact
     next-token table); n four-byte ones and a run too long for the window (the cut sequence); and
     blocks whose final literal-only sequence is number 0, 63 or 64."""
     out = {}
     for n in (1, 63, 64, 65, 127, 128, 129):
-        m = Maker(100 + n)
+        m = Maker(100 + n, base)
         seqs = m.short(n - 1)
         seqs.append(m.seq(CHUNK + 8 - 4 * n, 7))
         out[f"rows_{n}_run"] = (seqs + m.short(5), m.lits(6))
-        m = Maker(200 + n)
+        m = Maker(200 + n, base)
         seqs = m.short(n)
         seqs.append(m.seq(1400, 9))
         out[f"rows_{n}_cut"] = (seqs + m.short(70), m.lits(6))
     for n in (0, 63, 64):
-        m = Maker(300 + n)
+        m = Maker(300 + n, base)
         out[f"final_at_{n}"] = (m.short(n), m.lits(11))
     return out
 
 
-def cases_slow():
+def cases_slow(base=0):
     """Length fields of several bytes among >= 65 other sequences, in row 0 and in row 1: a literal
     length of 2 and of 3 extension bytes, a match length of 2+ bytes (the fast next-token table
     assumes one: the chunk is parsed again)."""
     out = {}
     for row, at in ((0, 10), (1, 80)):
         for name, ll, ml in (("ll2", 300, 6), ("ll3", 600, 6), ("ml2", 2, 4 + 15 + 255 + 40), ("ml3", 1, 4 + 15 + 600)):
-            m = Maker(400 + 10 * row + ll % 7 + ml % 5)
+            m = Maker(400 + 10 * row + ll % 7 + ml % 5, base)
             seqs = m.short(at) + [m.seq(ll, ml)] + m.short(90) + [m.seq(1500, 5)] + m.short(70)
             out[f"{name}_row{row}"] = (seqs, m.lits(5))
-            m = Maker(450 + 10 * row + ll % 7 + ml % 5)       # a short block: the exact table from the start
+            m = Maker(450 + 10 * row + ll % 7 + ml % 5, base)       # a short block: the exact table from the start
             out[f"{name}_row{row}_short"] = (m.short(at) + [m.seq(ll, ml)] + m.short(70), m.lits(5))
     return out
 
 
-def cases_redo():
+def cases_redo(base=0):
     """The fast next-token table sent back for the exact one: a match length field of 2 bytes and
     one of 3 bytes among the true tokens of one chunk, far enough from the block's end for the
     fast table. redo_2k: in the first chunk of a block of about 2 KiB (one segment). redo_seg1:
     past 5120 compressed bytes in a block of two segments, so that segment 1's parse -- the guess
     and, forced, the re-parse from segment 0's exit -- meets them too."""
     long2, long3 = 4 + 15 + 255 + 40, 4 + 15 + 600
-    m = Maker(600)
+    m = Maker(600, base)
     a = m.short(10) + [m.seq(2, long2)] + m.short(20) + [m.seq(1, long3)] + m.short(470)
     fa = m.lits(5)
-    m = Maker(601)
+    m = Maker(601, base)
     b = m.short(1300) + [m.seq(2, long2)] + m.short(20) + [m.seq(1, long3)] + m.short(1000)
     return {"redo_2k": (a, fa), "redo_seg1": (b, m.lits(5))}
 
@@ -186,17 +197,17 @@ def redo_cases():
     return done
 
 
-def build_cases():
+def build_cases(base=0):
     """name -> (compressed block, capacity, dictionary or None)."""
     cases = {}
-    s, f = case_dense()
+    s, f = case_dense(base)
     cases["dense3"] = (encode(s, f), None, None)
-    for group in (cases_rows(), cases_slow()):
+    for group in (cases_rows(base), cases_slow(base)):
         for name, (s, f) in group.items():
             cases[name] = (encode(s, f), None, None)
 
     def hundred(seed, edits):
-        m = Maker(seed)
+        m = Maker(seed, base)
         seqs = m.short(100)
         for k, fn in edits.items():
             lits, off, ml = seqs[k]
@@ -211,11 +222,11 @@ def build_cases():
     c, n = hundred(513, {})
     cases["cap_exact"] = (c, n, None)
     cases["cap_one_short"] = (c, n - 1, None)
-    m = Maker(514)
+    m = Maker(514, base)
     seqs = m.short(66) + [m.seq(12, 6)]
     full = encode(seqs, None)
     cases["malformed_and_offset0"] = (full[:full.size - 2 - 5].copy(), 2000, None)   # 5 of its 12 literals missing
-    m = Maker(515)
+    m = Maker(515, base)
     seqs = m.short(10)
     seqs += [m.seq(1, 8, off=m.pos + 1 + 300)] + m.short(53)                            # 300 bytes before the block
     d = m.lits(400)
@@ -224,13 +235,13 @@ def build_cases():
     return cases
 
 
-def fuzz_blocks():
+def fuzz_blocks(base=0):
     """200 seeded random token streams (<= 8 KiB each): short and long literal runs and matches,
     some with an offset of 0, a far offset, a truncated end or a capacity a few bytes off."""
     rng = np.random.default_rng(20240607)
     out = []
     for t in range(200):
-        m = Maker(1000 + t)
+        m = Maker(1000 + t, base)
         seqs, size = [], 0
         limit = int(rng.integers(40, 7000))
         while size < limit:
