@@ -917,24 +917,22 @@ int32_t lz4mi_frame_decompress(const uint8_t* frame, uint64_t len, uint8_t* out,
     uint8_t h[19] = {0};
     LZ4MI_TRY(hipMemcpyAsync(h, frame, std::min<uint64_t>(len, 19), hipMemcpyDeviceToHost, s));
     LZ4MI_TRY(hipStreamSynchronize(s));
+    lz4mi::frames::Walk w(h, std::min<uint64_t>(len, 19));
+    w.head();
     // magic and version as the device walk reports them (bufferDecompress.js:59-67), info[6] included
     info[6] = 4194304;
-    if (len < 4 || le32(h) != 0x184D2204u) {
-        info[0] = LZ4MI_ERR_MAGIC;
+    info[1] = w.flg;
+    if (w.err) {
+        info[0] = w.err;
         return LZ4MI_OK;
     }
-    info[1] = len > 4 ? h[4] : 0;
-    if (((info[1] & 0xC0) >> 6) != 1) {
-        info[0] = LZ4MI_ERR_VERSION;
-        return LZ4MI_OK;
-    }
-    const uint64_t size = (len >= 14 && (h[4] & 0x08)) ? (uint64_t)le32(h + 6) | ((uint64_t)le32(h + 10) << 32) : 0;
+    // (a size field that the frame's end cuts counts as none here, whatever bytes of it are present)
+    const uint64_t size = len >= 14 ? w.size : 0;
     info[2] = (int64_t)size;
     // no content size (or 0), or more than the caller's buffer: the host path decodes the frame;
     // checked before any scratch is sized from the header's claim
     if (size == 0 || size > out_cap) return LZ4MI_ERR_ARG;
-    const uint32_t id = len > 5 ? (h[5] >> 4) & 7 : 7;
-    const uint64_t bmax = id == 4 ? 65536 : id == 5 ? 262144 : id == 6 ? 1048576 : 4194304;
+    const uint64_t bmax = w.bmax;
     // every record takes at least its 4-byte size word
     const uint64_t cap_blocks = std::min<uint64_t>(size / bmax, len / 4) + 2;
     if (cap_blocks > 0xFFFFFFF0ull) return LZ4MI_ERR_ARG;

@@ -73,6 +73,61 @@ __device__ __forceinline__ uint32_t funnel(uint32_t lo, uint32_t hi, uint32_t sh
 // (stores acknowledged by L2). Also a compiler memory barrier.
 __device__ __forceinline__ void wait_vmem() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// n bytes from src to dst by the whole wave: 16-byte unaligned pieces, four in flight per lane, the last
+// one overlapping its predecessor.
+__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint64_t n, int lane) {
+    if (n < 16) {
+        if ((uint64_t)lane < n) dst[lane] = src[lane];
+        return;
+    }
+    const uint64_t np = (n + 15) / 16;
+    for (uint64_t p0 = 0; p0 < np; p0 += 4 * kWave) {
+        uint4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint64_t p = p0 + lane + kWave * u;
+            const uint64_t d = 16 * p < n - 16 ? 16 * p : n - 16;
+            if (p < np) __builtin_memcpy(&v[u], src + d, 16);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint64_t p = p0 + lane + kWave * u;
+            const uint64_t d = 16 * p < n - 16 ? 16 * p : n - 16;
+            if (p < np) __builtin_memcpy(dst + d, &v[u], 16);
+        }
+    }
+}
+
+// n zero bytes at dst by the whole wave: 16-byte pieces, the last one overlapping its predecessor.
+__device__ __forceinline__ void wave_zero(uint8_t* dst, uint64_t n, int lane) {
+    if (n < 16) {
+        if ((uint64_t)lane < n) dst[lane] = 0;
+        return;
+    }
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    const uint64_t np = (n + 15) / 16;
+    for (uint64_t p = lane; p < np; p += kWave) {
+        const uint64_t d = 16 * p < n - 16 ? 16 * p : n - 16;
+        __builtin_memcpy(dst + d, &z, 16);
+    }
+}
+
+// Block b's record of a frame at out[rec ..) by the whole wave: the LE32 size word, then the len payload
+// bytes from src. With block checksums (pay_off != nullptr) also the payload's place and length and the
+// checksum's place, for the batched XXH32 that fills the checksums in.
+__device__ __forceinline__ void wave_record(uint8_t* out, uint64_t rec, uint32_t word, const uint8_t* src, uint64_t len,
+                                            uint32_t b, uint64_t* pay_off, uint64_t* sum_off, uint32_t* pay_len,
+                                            int lane) {
+    uint8_t* dst = out + rec;
+    if (pay_off && lane == 0) {
+        pay_off[b] = rec + 4;
+        sum_off[b] = rec + 4 + len;
+        pay_len[b] = (uint32_t)len;
+    }
+    if (lane < 4) dst[lane] = (uint8_t)(word >> (8 * lane));
+    wave_copy(dst + 4, src, len, lane);
+}
+
 // Reads of bytes this wave (or workgroup) wrote earlier in the launch are plain
 // loads: the CU's L1 is coherent with the CU's own completed stores (the LLVM
 // AMDGPU memory model needs no L1 invalidate for workgroup scope on gfx950), and

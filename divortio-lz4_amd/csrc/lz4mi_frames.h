@@ -2,6 +2,8 @@
 // once for the device passes (lz4mi_frames.hip, one lane per frame) and for lz4mi_host_frames_index
 // (lz4mi_host.cpp, the calling thread): the walk of a frame's header and size words, the listing of its
 // blocks and the decoded size each block is given. finfo[f] is the eight values the header documents.
+// The single-frame calls (lz4mi_frame_index, lz4mi_frame_decompress; lz4mi_frame.hip, one lane) use the same
+// walk: index_frame and scan_frame, with lz4mi_host_frame_index / lz4mi_debug_frame_scan as their host twins.
 #pragma once
 #include <stdint.h>
 
@@ -18,7 +20,10 @@ namespace frames {
 
 enum { kErr = 0, kHead = 1, kSize = 2, kTotal = 3, kFirst = 4, kEnd = 5, kCount = 6, kDecline = 7 };
 
-// The walk of lz4mi_frame_index_kernel (bufferDecompress.js:56-92 header, :133-192 block loop) over
+// BLOCK_MAX_SIZES: the bytes of a BD byte's 3-bit block size id
+LZ4MI_HD uint32_t block_bytes(uint32_t id) { return id == 4 ? 65536u : id == 5 ? 262144u : id == 6 ? 1048576u : 4194304u; }
+
+// The reference's walk of a frame (bufferDecompress.js:56-92 header, :133-192 block loop) over
 // f[0 .. len): bytes past the end read as 0, nothing outside is read. Checks in the reference's order:
 // magic, version, then the size field, DictID and HC byte skipped.
 struct Walk {
@@ -31,6 +36,12 @@ struct Walk {
     LZ4MI_HD Walk(const uint8_t* f_, uint64_t len_) : f(f_), len(len_) {}
     LZ4MI_HD uint32_t rd(uint64_t p) const {
         uint32_t v = 0;
+        // the whole word lies inside: one load, not four that wait for each other (little-endian host and
+        // device: x86-64, gfx950)
+        if (len >= 4 && p <= len - 4) {
+            __builtin_memcpy(&v, f + p, 4);
+            return v;
+        }
         for (int k = 0; k < 4; ++k) v |= (p + k < len ? (uint32_t)f[p + k] : 0u) << (8 * k);
         return v;
     }
@@ -45,8 +56,7 @@ struct Walk {
             return;
         }
         bd = len > 5 ? f[5] : 0;
-        const uint32_t id = len > 5 ? (bd >> 4) & 7 : 7;
-        bmax = id == 4 ? 65536 : id == 5 ? 262144 : id == 6 ? 1048576 : 4194304;
+        bmax = block_bytes((bd >> 4) & 7);
         pos = 6;
         if (flg & 0x08) {
             size = (uint64_t)rd(pos) | ((uint64_t)rd(pos + 4) << 32);
@@ -72,10 +82,7 @@ struct Walk {
 // the LE32 behind the EndMark of a frame with a content checksum (FLG 0x04)
 constexpr int64_t kMeasured = 1 << 16;
 LZ4MI_HD bool sized(const int64_t* fi) { return (fi[kHead] & 0x08) && fi[kSize] != 0; }
-LZ4MI_HD uint32_t block_max(const int64_t* fi) {
-    const uint32_t id = (uint32_t)(fi[kHead] >> 12) & 7;
-    return id == 4 ? 65536 : id == 5 ? 262144 : id == 6 ? 1048576 : 4194304;
-}
+LZ4MI_HD uint32_t block_max(const int64_t* fi) { return block_bytes((uint32_t)(fi[kHead] >> 12) & 7); }
 // the blocks the frame has in the lists: none for a frame with a header error or one of the declines
 // that are known before the blocks are listed
 LZ4MI_HD uint64_t listed(const int64_t* fi) {
@@ -138,32 +145,41 @@ LZ4MI_HD void fill_frame(const uint8_t* f, uint64_t len, uint64_t frame_off, uin
     }
 }
 
+// The reference encoder's layout of a result of `size` bytes: the slot of each block in frame order. A
+// compressed block takes what is left of the result, block_max at most, and the position advances by
+// block_max; a stored block takes its declared size, and the reference advances by the declared size.
+// `size` is unsigned: a content size of 2^63 or more, which no caller has room for (lz4mi_frame_decompress
+// declines size > out_cap before it scans), leaves block_max, not 0 as a signed difference would.
+struct Layout {
+    uint64_t size, bmax, op = 0;   // op: the next block's position in the result
+
+    LZ4MI_HD Layout(uint64_t size_, uint64_t bmax_) : size(size_), bmax(bmax_) {}
+    LZ4MI_HD uint32_t slot(uint32_t word) {
+        if (word & 0x80000000u) {
+            op += word & 0x7FFFFFFFu;
+            return word & 0x7FFFFFFFu;
+        }
+        const uint64_t left = size > op ? size - op : 0;
+        op += bmax;
+        return (uint32_t)(left < bmax ? left : bmax);
+    }
+};
+
 // Sizes of one frame's listed blocks and its decoded total. A frame with a content size takes the
-// reference encoder's layout (lz4mi_frame_scan_kernel); a measured one the size walk's results
-// msize / mstatus (lz4mi_decoded_sizes over meas_word).
+// reference encoder's layout; a measured one the size walk's results msize / mstatus
+// (lz4mi_decoded_sizes over meas_word).
 LZ4MI_HD void size_frame(int64_t* fi, const uint32_t* blk_word, const uint32_t* msize, const int32_t* mstatus,
                          uint32_t* blk_size) {
     const uint64_t n = listed(fi), first = (uint64_t)fi[kFirst];
     if (n == 0) return;
-    const uint64_t size = (uint64_t)fi[kSize];
-    const uint64_t bmax = block_max(fi);
+    const uint64_t size = (uint64_t)fi[kSize], bmax = block_max(fi);
     if (fi[kDecline]) {   // (an unsized frame under LZ4MI_JS_EXACT: listed, not sized)
         for (uint64_t b = first; b < first + n; ++b) blk_size[b] = 0;
         return;
     }
     if (!(fi[kHead] & kMeasured)) {
-        uint64_t op = 0;
-        for (uint64_t b = first; b < first + n; ++b) {
-            const uint32_t word = blk_word[b], dn = word & 0x7FFFFFFFu;
-            if (word & 0x80000000u) {
-                blk_size[b] = dn;
-                op += dn;              // the reference advances by the declared size
-            } else {
-                const uint64_t left = size > op ? size - op : 0;
-                blk_size[b] = (uint32_t)(left < bmax ? left : bmax);
-                op += bmax;
-            }
-        }
+        Layout lay(size, bmax);
+        for (uint64_t b = first; b < first + n; ++b) blk_size[b] = lay.slot(blk_word[b]);
         fi[kTotal] = (int64_t)size;
         return;
     }
@@ -179,6 +195,84 @@ LZ4MI_HD void size_frame(int64_t* fi, const uint32_t* blk_word, const uint32_t* 
     fi[kTotal] = (int64_t)total;
     if (bad || (!sized(fi) && comp_max > bmax)) fi[kDecline] = LZ4MI_FRAMES_DECLINE_MEASURE;
     else if (sized(fi) && total != size) fi[kDecline] = LZ4MI_FRAMES_DECLINE_SIZE_MISMATCH;
+}
+
+// ------------------------------------------------------------------------ the single-frame calls
+// The eight info words of lz4mi_frame_index / lz4mi_frame_decompress after a walk: status, FLG, content size,
+// the two counts, the position the walk stopped at, block_max, and 1 when it ended behind the frame or the
+// lists were full. A header error leaves everything behind FLG at its initial value.
+LZ4MI_HD void walk_info(const Walk& w, uint32_t n3, uint32_t n4, bool full, int64_t* info) {
+    info[0] = w.err;
+    info[1] = w.flg;
+    info[2] = (int64_t)w.size;
+    info[3] = n3;
+    info[4] = n4;
+    info[5] = (int64_t)w.pos;
+    info[6] = w.bmax;
+    info[7] = full || w.pos > w.len;
+}
+
+// lz4mi_frame_index of one frame: every block in frame order, payload position and raw size word. When the
+// lists are full nothing more is written and the walk stops behind the size word of the first block that
+// did not fit.
+LZ4MI_HD void index_frame(const uint8_t* f, uint64_t len, uint32_t cap_blocks, uint64_t* pay_off, uint32_t* size_word,
+                          int64_t* info) {
+    Walk w(f, len);
+    w.head();
+    uint32_t n = 0;
+    bool full = false;
+    uint64_t pay;
+    uint32_t word;
+    while (!w.err && w.next(pay, word)) {
+        if (n == cap_blocks) {
+            full = true;
+            w.pos = pay;
+            break;
+        }
+        pay_off[n] = pay;
+        size_word[n] = word;
+        ++n;
+    }
+    walk_info(w, n, 0, full, info);
+}
+
+// The block lists of lz4mi_frame_decompress: compressed and stored blocks apart (c_idx / s_idx: the block's
+// index in frame order), each with its slot of the reference encoder's layout. The caller checks the decoded
+// lengths against the slots. Full lists: as in index_frame.
+LZ4MI_HD void scan_frame(const uint8_t* f, uint64_t len, uint32_t cap_blocks, uint64_t* c_in_off, uint32_t* c_in_len,
+                         uint64_t* c_out_off, uint32_t* c_out_cap, uint64_t* s_in_off, uint32_t* s_len,
+                         uint64_t* s_out_off, uint32_t* c_idx, uint32_t* s_idx, int64_t* info) {
+    Walk w(f, len);
+    w.head();
+    Layout lay(w.size, w.bmax);
+    uint32_t nc = 0, ns = 0;
+    bool full = false;
+    uint64_t pay;
+    uint32_t word;
+    while (!w.err && w.next(pay, word)) {
+        if (nc + ns == cap_blocks) {
+            full = true;
+            w.pos = pay;
+            break;
+        }
+        const uint64_t at = lay.op;
+        const uint32_t slot = lay.slot(word);
+        if (word & 0x80000000u) {
+            s_in_off[ns] = pay;
+            s_len[ns] = slot;
+            s_out_off[ns] = at;
+            s_idx[ns] = nc + ns;
+            ++ns;
+        } else {
+            c_in_off[nc] = pay;
+            c_in_len[nc] = word;
+            c_out_off[nc] = at;
+            c_out_cap[nc] = slot;
+            c_idx[nc] = nc + ns;
+            ++nc;
+        }
+    }
+    walk_info(w, nc, ns, full, info);
 }
 
 }  // namespace frames

@@ -158,20 +158,6 @@ __global__ __launch_bounds__(64) void lz4mi_frames_place_kernel(int64_t* finfo, 
     }
 }
 
-// n zero bytes at dst by the whole wave: 16-byte pieces, the last one overlapping its predecessor.
-__device__ __forceinline__ void wave_zero(uint8_t* dst, uint64_t n, int lane) {
-    if (n < 16) {
-        if ((uint64_t)lane < n) dst[lane] = 0;
-        return;
-    }
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    const uint64_t np = (n + 15) / 16;
-    for (uint64_t p = lane; p < np; p += kWave) {
-        const uint64_t d = 16 * p < n - 16 ? 16 * p : n - 16;
-        __builtin_memcpy(dst + d, &z, 16);
-    }
-}
-
 // Finish pass: one wave per frame over its blocks' statuses and lengths, in block order. With
 // LZ4MI_FRAMES_CHAINS (`word` is then blk_word) only the blocks up to and including the first failing one decide
 // whether the frame is declined: behind it the chain left LZ4MI_ERR_CROSS_BLOCK and length 0 (the after-failure

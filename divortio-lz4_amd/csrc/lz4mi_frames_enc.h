@@ -8,12 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/lz4mi.h"
-
-#if defined(__HIPCC__)
-#define LZ4MI_HD __host__ __device__ inline
-#else
-#define LZ4MI_HD inline
-#endif
+#include "lz4mi_frames.h"   // LZ4MI_HD, frames::block_bytes
 
 namespace lz4mi {
 namespace frames_enc {
@@ -41,11 +36,11 @@ inline bool bad_compress_args(const void* in, const void* blk_in_off, const void
     return nblocks && (!in || !blk_in_off || !blk_len || !blk_frame || !blk_work_off || !work || work_bytes < kDump);
 }
 
-// getBlockId (bufferCompress.js:77-82) and BLOCK_MAX_SIZES
+// getBlockId (bufferCompress.js:77-82); its inverse is frames::block_bytes
 LZ4MI_HD uint32_t block_id(uint32_t bytes) {
     return (!bytes || bytes <= 65536u) ? 4 : bytes <= 262144u ? 5 : bytes <= 1048576u ? 6 : 7;
 }
-LZ4MI_HD uint32_t block_bytes(uint32_t id) { return id == 4 ? 65536u : id == 5 ? 262144u : id == 6 ? 1048576u : 4194304u; }
+using frames::block_bytes;
 LZ4MI_HD uint32_t block_max(const int64_t* fi) { return block_bytes((uint32_t)(fi[kHead] >> 12) & 7); }
 // (bmax is one of the four block sizes, a power of two: no 64-bit division in the lane-per-frame passes)
 LZ4MI_HD uint64_t block_count(uint64_t n, uint32_t bmax) {

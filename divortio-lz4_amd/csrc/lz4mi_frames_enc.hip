@@ -176,35 +176,9 @@ __global__ __launch_bounds__(64) void lz4mi_frames_enc_write_kernel(const int64_
     write_frame(finfo + 8ull * f, out, blk_in_off, blk_len, comp_len, rec_off, hash_off + f, hash_len + f, hash_dst + f);
 }
 
-// n bytes from src to dst by the whole wave: 16-byte unaligned pieces, the last one overlapping its predecessor
-// (the copy of lz4mi_frame_pack_kernel).
-__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint64_t n, int lane) {
-    if (n < 16) {
-        if ((uint64_t)lane < n) dst[lane] = src[lane];
-        return;
-    }
-    const uint64_t np = (n + 15) / 16;
-    for (uint64_t p0 = 0; p0 < np; p0 += 4 * kWave) {
-        uint4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint64_t p = p0 + lane + kWave * u;
-            const uint64_t d = 16 * p < n - 16 ? 16 * p : n - 16;
-            if (p < np) __builtin_memcpy(&v[u], src + d, 16);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint64_t p = p0 + lane + kWave * u;
-            const uint64_t d = 16 * p < n - 16 ? 16 * p : n - 16;
-            if (p < np) __builtin_memcpy(dst + d, &v[u], 16);
-        }
-    }
-}
-
 // Pack pass: one wave per listed block whose frame is written (rec_off[b] != kNone): the record's size word and
-// payload, as lz4mi_frame_pack_kernel writes them; with block checksums (pay_off != nullptr) also the payload's
-// place and length and the checksum's place for the batched XXH32 (the caller has set sum_off to kNone and
-// pay_len to 0 for every block).
+// payload (wave_record; with block checksums the caller has set sum_off to kNone and pay_len to 0 for every
+// block).
 __global__ __launch_bounds__(64) void lz4mi_frames_enc_pack_kernel(const uint8_t* in, const uint64_t* blk_in_off,
                                                                    const uint32_t* blk_len, const uint8_t* work,
                                                                    const uint64_t* enc_off, const uint32_t* comp_len,
@@ -218,17 +192,8 @@ __global__ __launch_bounds__(64) void lz4mi_frames_enc_pack_kernel(const uint8_t
     if (rec == kNone) return;
     const uint32_t n = blk_len[b], cl = comp_len[b];
     const bool st = stored(cl, n);
-    const uint32_t word = st ? (n | 0x80000000u) : cl;
-    const uint8_t* src = st ? in + blk_in_off[b] : work + enc_off[b];
-    const uint64_t len = st ? n : cl;
-    uint8_t* dst = out + rec;
-    if (pay_off && lane == 0) {
-        pay_off[b] = rec + 4;
-        sum_off[b] = rec + 4 + len;
-        pay_len[b] = (uint32_t)len;
-    }
-    if (lane < 4) dst[lane] = (uint8_t)(word >> (8 * lane));
-    wave_copy(dst + 4, src, len, lane);
+    wave_record(out, rec, st ? (n | 0x80000000u) : cl, st ? in + blk_in_off[b] : work + enc_off[b], st ? n : cl, b,
+                pay_off, sum_off, pay_len, lane);
 }
 
 }  // namespace frames_enc

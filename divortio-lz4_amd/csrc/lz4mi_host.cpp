@@ -423,6 +423,25 @@ extern "C" int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* fr
     return LZ4MI_OK;
 }
 
+// lz4mi_frame_index on the calling thread (include/lz4mi.h): the function its kernel's one lane calls.
+extern "C" int32_t lz4mi_host_frame_index(const uint8_t* frame, uint64_t len, uint64_t* pay_off, uint32_t* size_word,
+                                          uint32_t cap_blocks, int64_t* info) {
+    if ((!frame && len) || !info || (cap_blocks && (!pay_off || !size_word))) return LZ4MI_ERR_ARG;
+    lz4mi::frames::index_frame(frame, len, cap_blocks, pay_off, size_word, info);
+    return LZ4MI_OK;
+}
+
+// The block lists lz4mi_frame_decompress gets from its scan kernel, on the calling thread into the caller's
+// arrays of cap_blocks entries each (tests/test_frame_walk_cpu.py).
+extern "C" int lz4mi_debug_frame_scan(const uint8_t* frame, uint64_t len, uint32_t cap_blocks, uint64_t* c_in_off,
+                                      uint32_t* c_in_len, uint64_t* c_out_off, uint32_t* c_out_cap, uint64_t* s_in_off,
+                                      uint32_t* s_len, uint64_t* s_out_off, uint32_t* c_idx, uint32_t* s_idx,
+                                      int64_t* info) {
+    lz4mi::frames::scan_frame(frame, len, cap_blocks, c_in_off, c_in_len, c_out_off, c_out_cap, s_in_off, s_len, s_out_off,
+                              c_idx, s_idx, info);
+    return 0;
+}
+
 // lz4mi_frames_plan / lz4mi_frames_compress on the calling thread (include/lz4mi.h): the same per-frame steps
 // (lz4mi_frames_enc.h) in the device passes' order -- count, exclusive scans, fill; prep, encode, size, position,
 // write, pack, checksums -- with lz4mi_host_compress_block and a fresh table per block as the encoder, or one

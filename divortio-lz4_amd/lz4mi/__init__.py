@@ -60,8 +60,8 @@ EXPORTS = ("lz4mi_status_message", "lz4mi_init", "lz4mi_device_count", "lz4mi_ve
            "lz4mi_host_compress_block", "lz4mi_host_compress_chain", "lz4mi_host_decompress_block",
            "lz4mi_decoded_sizes", "lz4mi_host_decoded_size", "lz4mi_host_block_read_end",
            "lz4mi_verify_blocks", "lz4mi_host_verify_blocks", "lz4mi_frames_index", "lz4mi_frames_decompress",
-           "lz4mi_host_frames_index", "lz4mi_frame_bound", "lz4mi_frames_plan", "lz4mi_frames_compress",
-           "lz4mi_host_frames_plan", "lz4mi_host_frames_compress")
+           "lz4mi_host_frames_index", "lz4mi_host_frame_index", "lz4mi_frame_bound", "lz4mi_frames_plan",
+           "lz4mi_frames_compress", "lz4mi_host_frames_plan", "lz4mi_host_frames_compress")
 
 
 class Lz4miError(RuntimeError):
@@ -149,6 +149,8 @@ def lib():
         L.lz4mi_host_frames_index.restype = ctypes.c_int32
         L.lz4mi_host_frames_index.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
                                               _vp, ctypes.c_uint32]
+        L.lz4mi_host_frame_index.restype = ctypes.c_int32
+        L.lz4mi_host_frame_index.argtypes = [_vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp]
         L.lz4mi_frame_bound.restype = ctypes.c_uint64
         L.lz4mi_frame_bound.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
         plan = [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32]
@@ -513,6 +515,17 @@ def host_frames_index(arena, frame_off, frame_len, cap_blocks, measure=False, js
                                          res["totals"].ctypes.data,
                                          (FRAMES_MEASURE if measure else 0) | (JS_EXACT if js_exact else 0)))
     return res
+
+
+def host_frame_index(frame, pay_off, size_word, cap_blocks, info):
+    """lz4mi_frame_index on the calling thread (lz4mi_host_frame_index, no device needed) into the caller's
+    arrays: pay_off (uint64) and size_word (uint32), of which the first cap_blocks entries may be written, and
+    info (8 x int64)."""
+    a = _u8(frame)
+    assert pay_off.dtype == np.uint64 and size_word.dtype == np.uint32 and info.dtype == np.int64 and info.size == 8
+    assert cap_blocks <= min(pay_off.size, size_word.size)
+    src = a if a.size else np.zeros(1, dtype=np.uint8)   # (an empty frame still needs an address)
+    _check(lib().lz4mi_host_frame_index(_p(src), a.size, _p(pay_off), _p(size_word), cap_blocks, _p(info)))
 
 
 def frame_bound(n, block_max=4194304):

@@ -494,7 +494,7 @@ def compress_frame_sharded(raw, block_size=4194304, content_checksum=True, add_c
     root), checksum (host-staged content checksum), assemble (header + EndMark on root)."""
     import time
     import torch
-    block_size = {4: 65536, 5: 262144, 6: 1048576, 7: 4194304}[block_id(block_size)]
+    block_size = shard.BLOCK_MAX_SIZES[block_id(block_size)]
     codec = codec or DeviceCodec()
     dist, multi, world, rank = _dist_ctx(group)
     n = raw.numel()
@@ -889,7 +889,7 @@ def _decode_measured(frame, head, js_exact, s, linked=False, verify_blocks=False
     dev = frame.device
     n = frame.numel()
     bid = (int(head[5]) >> 4) & 7 if head.size > 5 else 7
-    bmax = {4: 65536, 5: 262144, 6: 1048576}.get(bid, 4194304)
+    bmax = shard.BLOCK_MAX_SIZES.get(bid, 4194304)
     # the block lists are sized by walking the frame: first for the blocks it would have at a
     # compression ratio of 4, then, while the walk reports more blocks than listed, 16x as many
     # (never n / 4 entries up front: every record takes at least its 4-byte size word)
@@ -1331,7 +1331,7 @@ def compress_frames_device(buffers, block_size=4194304, independent=True, conten
     report.update(routes=[None] * nf, declined=[0] * nf)
     if nf == 0:
         return []
-    bs = {4: 65536, 5: 262144, 6: 1048576, 7: 4194304}[block_id(block_size)]
+    bs = shard.BLOCK_MAX_SIZES[block_id(block_size)]
     flags = lz4mi.frames_enc_flags(independent, content_checksum, add_content_size, block_checksum, packed=True,
                                    chains=chains)
     lz4mi.init(dev.index if dev.index is not None else torch.cuda.current_device())

@@ -441,7 +441,9 @@ int64_t lz4mi_host_block_read_end(const uint8_t* in, uint64_t in_total, int64_t 
  * header and the size words and writes, per block in frame order, the payload position
  * (pay_off) and the raw size word (size_word, bit 31 = stored). info (8 x int64, device)
  * as lz4mi_frame_decompress's, with [3] = blocks listed, [7] = 1 when the walk ran past
- * the frame or past cap_blocks. Device pointers only (LZ4MI_DEVICE_PTRS); asynchronous
+ * the frame or past cap_blocks. Past cap_blocks, [3] is cap_blocks, no entry behind it is
+ * written, and [5] is the position behind the size word of the first block that did not
+ * fit. Device pointers only (LZ4MI_DEVICE_PTRS); asynchronous
  * on `stream`. Replaces nothing in the reference (its frame loop is serial in one call).
  */
 int32_t lz4mi_frame_index(const uint8_t* frame, uint64_t len, uint64_t* pay_off, uint32_t* size_word,
@@ -550,6 +552,12 @@ int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* frame_off, co
                                 uint32_t nframes, uint64_t* blk_in_off, uint32_t* blk_word, uint32_t* blk_frame,
                                 uint32_t* blk_size, uint32_t cap_blocks, int64_t* finfo, int64_t* totals,
                                 uint32_t flags);
+/*
+ * lz4mi_frame_index on the calling thread (host pointers, no device needed): the checker of the single-frame
+ * walk, the same function the kernel's lane runs. info as lz4mi_frame_index's.
+ */
+int32_t lz4mi_host_frame_index(const uint8_t* frame, uint64_t len, uint64_t* pay_off, uint32_t* size_word,
+                               uint32_t cap_blocks, int64_t* info);
 
 /*
  * A BATCH OF BUFFERS compressed into one LZ4 frame each on the device: plan, then compress. Device pointers only

@@ -195,6 +195,88 @@ def test_frame_pack(block_checksum):
         assert np.array_equal(d_raw.cpu().numpy(), data) and np.array_equal(d_comp.cpu().numpy(), comp)
 
 
+# payload lengths at the edges of the whole-wave copy (wave_copy, csrc/lz4mi_common.h): below one 16-byte piece,
+# around one and two pieces, around one full trip of its loop (4 x 64 lanes x 16 bytes = 4096), and two trips
+COPY_EDGES = (0, 1, 15, 16, 17, 31, 32, 33, 4095, 4096, 4097, 8197)
+
+
+def _le32(x):
+    return np.array([x & 0xFFFFFFFF], dtype="<u4").view(np.uint8)
+
+
+def test_wave_copy_edges():
+    """(a) lz4mi_frame_pack: per length L > 0 one stored record (comp_len 0, raw_len L) and one compressed record
+    (comp_len L of arbitrary bytes, raw_len L + 1), at odd rec_off with a few bytes between two records, the
+    sources at all sixteen address residues, with and without block checksums: size word, payload and the
+    spec XXH32 assembled in numpy, nothing else written.
+    (b) lz4mi_frame_decompress: stored blocks of every length, content size their sum, at an odd frame and an
+    odd output address: the output is their concatenation, nothing outside out[0 .. content size) is written
+    (the 4 KiB behind out_cap, the margins). The call sizes its lists from content size / block_max, two blocks
+    for these sizes, and declines a frame with more (the parent commit's library too): so the lengths go
+    through it as six frames of two stored blocks each."""
+    rng = np.random.default_rng(720)
+    # ---- (a)
+    recs = [(L, stored) for L in COPY_EDGES if L for stored in (True, False)]
+    src_off, at = [], 0
+    for k, (L, _) in enumerate(recs):
+        at += (k % 16 - at) % 16
+        src_off.append(at)
+        at += L + 16
+    assert {o % 16 for o in src_off} == set(range(16))
+    raw, comp = rng.integers(0, 256, at, dtype=np.uint8), rng.integers(0, 256, at, dtype=np.uint8)
+    for block_checksum in (False, True):
+        rec_off, sizes, at = [], [], 1
+        for k, (L, _) in enumerate(recs):
+            rec_off.append(at)
+            sizes.append(4 + L + (4 if block_checksum else 0))
+            at = (at + sizes[-1] + 5 + 2 * (k % 3)) | 1    # (every rec_off odd)
+        assert all(o % 2 for o in rec_off)
+        span = at
+        d_raw, d_comp = _t(raw, np.uint8), _t(comp, np.uint8)
+        d_off = _t(src_off, np.int64)
+        d_rlen = _t([L if st else L + 1 for L, st in recs], np.int32)
+        d_clen = _t([0 if st else L for L, st in recs], np.int32)
+        d_rec = _t(rec_off, np.int64)
+        for run in (0, 1):
+            init = F.pattern(2 * MARGIN + span, run)
+            image = init.copy()
+            for (L, st), so, ro in zip(recs, src_off, rec_off):
+                pay = (raw if st else comp)[so:so + L]
+                parts = [_le32(L | (0x80000000 if st else 0)), pay] + ([_le32(O.xxh32_std(pay))] if block_checksum else [])
+                r = np.concatenate(parts)
+                image[MARGIN + ro:MARGIN + ro + r.size] = r
+            d_frame = _t(init, np.uint8)
+            lz4mi.frame_pack_dev(d_raw.data_ptr(), d_off.data_ptr(), d_rlen.data_ptr(), d_comp.data_ptr(), d_off.data_ptr(),
+                                 d_clen.data_ptr(), d_frame.data_ptr() + MARGIN, d_rec.data_ptr(), len(recs), _stream(),
+                                 block_checksum=block_checksum)
+            torch.cuda.synchronize()
+            F.assert_footprint(d_frame.cpu().numpy(), image, np.ones(image.size, dtype=bool), F.Regions(rec_off, sizes),
+                               f"frame_pack copy edges, checksums {block_checksum}, run {run}")
+            assert np.array_equal(d_raw.cpu().numpy(), raw) and np.array_equal(d_comp.cpu().numpy(), comp)
+    # ---- (b)
+    from lz4mi import frame as FR
+    seen = []
+    for k in range(0, len(COPY_EDGES), 2):
+        pays = [rng.integers(0, 256, L, dtype=np.uint8) for L in COPY_EDGES[k:k + 2]]
+        seen += [p.size for p in pays]
+        size = sum(p.size for p in pays)
+        head = np.frombuffer(FR.header(65536, True, False, size), dtype=np.uint8)
+        f = np.concatenate([head] + [x for p in pays for x in (_le32(p.size | 0x80000000), p)] + [_le32(0)])
+        d_f = torch.zeros(f.size + 3, dtype=torch.uint8, device="cuda")
+        d_f[3:] = torch.from_numpy(f).cuda()
+        for run in (0, 1):
+            init = F.pattern(2 * MARGIN + 1 + size, run)
+            d_out = _t(init, np.uint8)
+            info = lz4mi.frame_decompress_dev(d_f.data_ptr() + 3, f.size, d_out.data_ptr() + MARGIN + 1, size, _stream())
+            torch.cuda.synchronize()
+            assert (info["status"], info["content_size"], info["written"], info["stored_blocks"]) == (0, size, size, 2)
+            image = init.copy()
+            image[MARGIN + 1:MARGIN + 1 + size] = np.concatenate(pays)
+            F.assert_footprint(d_out.cpu().numpy(), image, np.ones(image.size, dtype=bool), F.Regions([1], [size]),
+                               f"frame_decompress stored {[p.size for p in pays]} run {run}")
+    assert tuple(seen) == COPY_EDGES
+
+
 @pytest.mark.parametrize("bsize", [4099, 8190])
 def test_generate_blocks(bsize):
     """lz4mi_generate_blocks writes out[0 .. nblocks * bsize) and nothing else."""
