@@ -9,8 +9,8 @@
 // exactly; the wave's 64 lanes make each step wide (speculative probe batches,
 // 128-byte window compares, emission) instead of making the chain parallel.
 // Three kernels:
-//   lz4mi_compress_gts_kernel    independent blocks, one wave per block, 16 per CU
-//                                (global 15-bit tables + LDS epoch codes);
+//   lz4mi_compress_gts_kernel    independent blocks, one wave per block (15-bit tables in
+//                                global memory or LDS + LDS epoch codes; blocks per CU at GtsShared);
 //   lz4mi_compress_chain_kernel  dependent blocks / one block with the caller's
 //                                table (LZ4.compressRaw): one wave, the table, the
 //                                source window and the output ring in LDS;
@@ -68,7 +68,6 @@ struct CompArgs {
 
 constexpr uint32_t kP1 = 2654435761u;
 
-
 __device__ __forceinline__ uint32_t src_byte(const CompJob& j, int64_t p) {
     return (p >= 0 && (uint64_t)p < j.src_total) ? (uint32_t)j.src[p] : 0u;
 }
@@ -77,10 +76,8 @@ __device__ __forceinline__ uint32_t src_byte(const CompJob& j, int64_t p) {
 // SGPR spills, round 4).
 __device__ __forceinline__ int32_t group_val(int32_t v, int g) { return __shfl(v, g, kWave); }
 
-// Lane l gets v of lane 8 (l & 7) + f, f = the first set bit of byte (l & 7) of mm (0 when
-// the byte is 0; `ft` is that lane's own f): one LDS permute.
-__device__ __forceinline__ uint32_t first_val(uint32_t v, uint64_t mm, int lane, int ft) {
-    (void)mm;
+// Lane l gets v of lane 8 (l & 7) + ft (`ft`: that lane's own choice among its group's lanes): one LDS permute.
+__device__ __forceinline__ uint32_t first_val(uint32_t v, int lane, int ft) {
     return __shfl(v, 8 * (lane & 7) + ft, kWave);
 }
 
@@ -209,7 +206,7 @@ __device__ int64_t match_extent(const CompJob& j, int lane, int64_t a, int64_t b
 __device__ __forceinline__ void settle32(uint32_t& v) { asm volatile("" : "+v"(v)); }
 
 // ---------------------------------------------------------------------------
-// Batch encoder (fresh table per block): the same parse, 4 blocks per CU.
+// Batch encoder (fresh table per block): the same parse.
 //
 // Table: a block's positions fit 22 bits, but a candidate only matters while
 // it is < 65536 bytes back, so each entry keeps the position's low 16 bits plus
@@ -234,12 +231,10 @@ constexpr int kCodeWords = 16384 / 16;
 #define RING_MASK(F) (RING_SZ(F) - 1)
 constexpr int32_t kDirectLit = 2048;   // longer literal runs bypass the ring
 
-
 struct FastOut {
     uint8_t* dst;
     int64_t op, flushed;   // flushed is 16-aligned except after the final flush
 };
-
 
 // ring [flushed, floor16(op)) -> dst
 template <class SH>
@@ -286,9 +281,8 @@ __device__ __forceinline__ void ring_len_ext(SH& F, FastOut& o, int lane, int64_
 }
 
 // src[pos, pos+n) -> output at op
-template <class SH, class SRC = SrcG>
-__device__ void ring_copy(SH& F, FastOut& o, const CompJob& j, int lane, int64_t pos, int64_t n,
-                          const Ring* rg = nullptr) {
+template <class SH, class SRC>
+__device__ void ring_copy(SH& F, FastOut& o, const CompJob& j, int lane, int64_t pos, int64_t n, const Ring* rg) {
     // a run through the ring must fit beside the <= 15 bytes a flush leaves pending: the
     // batch encoder's 2 KiB ring takes at most 2032 (2034..2048 wrapped onto those bytes)
     constexpr int64_t kViaRing = RING_SZ(F) - 16 < kDirectLit ? RING_SZ(F) - 16 : kDirectLit;
@@ -331,15 +325,13 @@ __device__ void ring_copy(SH& F, FastOut& o, const CompJob& j, int lane, int64_t
 }
 
 // token + literal length + literals
-template <class SH, class SRC = SrcG>
+template <class SH, class SRC>
 __device__ void fast_literals(SH& F, FastOut& o, const CompJob& j, int lane, int64_t anchor, int64_t lit,
-                              uint32_t mnib, const Ring* rg = nullptr) {
+                              uint32_t mnib, const Ring* rg) {
     ring_put(F, o, lane, (lit >= 15 ? 0xF0u : (uint32_t)lit << 4) | mnib);
     if (lit >= 15) ring_len_ext(F, o, lane, lit - 15);
     if (lit) ring_copy<SH, SRC>(F, o, j, lane, anchor, lit, rg);
 }
-
-
 
 // The miss-chain distance covered by the skip steps (c + t) >> 6, t < k: the sum of floor(u / 64)
 // over u in [c, c + k), k < 64, in 32-bit arithmetic (floor(u / 64) is c >> 6, then at most once
@@ -353,7 +345,7 @@ __device__ __forceinline__ int32_t skip_span(uint32_t c, uint32_t k) {
 // out of line with the output state passed by value and returned: inlining it at every
 // emission site costs the batch encoders their registers, and a FastOut passed by reference
 // to a call lives in scratch memory (every emission then reads it back with a vmcnt(0) wait).
-template <class SH, class SRC = SrcG>
+template <class SH, class SRC>
 __device__ __noinline__ FastOut emit_general(SH& F, FastOut o, const CompJob& j, int lane, int32_t anchor, int32_t pm,
                                              uint32_t off, int32_t mcode, const Ring* rg) {
     const int32_t lit = pm - anchor;
@@ -366,7 +358,7 @@ __device__ __noinline__ FastOut emit_general(SH& F, FastOut o, const CompJob& j,
 }
 
 // The final literal run (out of line, as emit_general).
-template <class SH, class SRC = SrcG>
+template <class SH, class SRC>
 __device__ __noinline__ FastOut emit_tail(SH& F, FastOut o, const CompJob& j, int lane, int64_t anchor, int64_t lit,
                                           const Ring* rg) {
     fast_literals<SH, SRC>(F, o, j, lane, anchor, lit, 0, rg);
@@ -376,10 +368,10 @@ __device__ __noinline__ FastOut emit_tail(SH& F, FastOut o, const CompJob& j, in
 // One sequence's bytes: token, literal length, literals, offset, match length.
 // Common case (at most 14 literals, match length field of at most one extra
 // byte) written by one ds_write_b8 per lane.
-template <class SH, class SRC = SrcG>
+template <class SH, class SRC>
 __device__ __forceinline__ void emit_seq(SH& F, FastOut& o, const CompJob& j, int lane, int32_t anchor,
-                                         int32_t pm, uint32_t off, int32_t mcode, const Ring* rg = nullptr,
-                                         bool has_pre = false, uint32_t pre = 0) {
+                                         int32_t pm, uint32_t off, int32_t mcode, const Ring* rg, bool has_pre,
+                                         uint32_t pre) {
     const int32_t lit = pm - anchor;
     const uint32_t mnib = mcode >= 15 ? 15u : (uint32_t)mcode;
     if (lit < 15 && mcode < 15 + 255) {
@@ -399,7 +391,6 @@ __device__ __forceinline__ void emit_seq(SH& F, FastOut& o, const CompJob& j, in
     }
     o = emit_general<SH, SRC>(F, o, j, lane, anchor, pm, off, mcode, rg);
 }
-
 
 // A batch's common-case sequences into the ring (lanes k < npend: sequence k at ring offset
 // start, `total` bytes in all; sequence 0 alone has literals, lit0 < 15, whose byte l - 1 lane
@@ -423,7 +414,6 @@ __device__ __forceinline__ void ring_seqs(SH& F, FastOut& o, int lane, int npend
     if (lane >= 1 && lane <= lit0) F.ring[(base + (uint32_t)lane) & msk] = (uint8_t)litv;
     o.op += total;
 }
-
 
 // ---------------------------------------------------------------------------
 // Batch encoder tables: one per block in global scratch, each entry the probed
@@ -451,7 +441,6 @@ __device__ void gt_scrub_epoch(SH& F, int lane, int32_t g) {
     }
 }
 
-
 // ---------------------------------------------------------------------------
 // Speculative hit chains (round 3, default). After a hit of step S (match end -
 // probe position) the next probe is at the match end, and on mid-ratio data the
@@ -476,7 +465,8 @@ __device__ void gt_scrub_epoch(SH& F, int lane, int32_t g) {
 constexpr int kSpecK = 8;     // probes per speculative batch (8 lanes each for the windows)
 constexpr int kSpecW = 128;   // window bytes per probe
 
-// 16 source bytes at p (zero past the end).
+// 16 source bytes at p (zero past the end). The batch encoder's loads too: 32-bit offsets from
+// the block's scalar base instead were slower (77.9 vs 74.9 ms, round 4).
 __device__ __forceinline__ uint4 ld16(const CompJob& j, int64_t p) {
     uint4 v;
     if (p >= 0 && (uint64_t)p + 16 <= j.src_total) {
@@ -484,17 +474,6 @@ __device__ __forceinline__ uint4 ld16(const CompJob& j, int64_t p) {
         return v;
     }
     return make_uint4(ld_u32(j, p), ld_u32(j, p + 4), ld_u32(j, p + 8), ld_u32(j, p + 12));
-}
-
-// The batch encoder's loads (zero outside the block). 32-bit offsets from the block's scalar
-// base instead were slower (77.9 vs 74.9 ms, round 4).
-__device__ __forceinline__ uint4 ld16o(const CompJob& j, uint32_t lim, int32_t p) {
-    (void)lim;
-    return ld16(j, p);
-}
-__device__ __forceinline__ uint32_t ld_u32o(const CompJob& j, uint32_t lim, int32_t p) {
-    (void)lim;
-    return ld_u32(j, p);
 }
 
 // Index of the first nonzero byte of x (16 if none).
@@ -506,17 +485,22 @@ __device__ __forceinline__ uint32_t first_nz16(uint4 x) {
 
 constexpr int32_t kWinBytes = 2048;   // source window in LDS: the probes' 4-byte reads
 
+// Blocks per CU: a block is one wave, so kWavesPerSimd (the kernel's __launch_bounds__ minimum,
+// which caps its registers) x 4 SIMDs, where the CU's 160 KiB of LDS admit that many. GtsShared:
+// 9 232 B, 4 waves per SIMD (at most 128 VGPRs), 16 blocks per CU (LDS would take 17).
 struct GtsShared {
+    static constexpr int kWavesPerSimd = 4;
     uint8_t ring[2048];                  // output ring (half the batch encoder's: the window takes the rest)
     uint8_t slot[1024];                  // miss batches: lane ids keyed by hash & 1023
     uint32_t code[kCodeWords];           // 2-bit epoch code per table entry
     uint32_t win[kWinBytes / 4 + 4];     // source bytes [wb, wb + kWinBytes)
 };
-// Small batches (<= kLdsTableMaxBlocks): the 15-bit table in LDS too (41 KB per block, 3 blocks
-// per CU, the batch one resident round): 1 block 26.7 -> 25.5 ms, 16: 32.4 -> 31.2, 256: 34.5
-// -> 32.9, 768: 42.4 -> 37.7 (profiles/r05f2/ldst_small.log); at 4096 blocks it needs 5.3 rounds
-// (200 vs 70 ms, profiles/r05n)
+// Small batches (<= kLdsTableMaxBlocks): the 15-bit table in LDS too (42 000 B per block: LDS
+// admits 3 blocks per CU, under one wave per SIMD; the batch is one resident round): 1 block
+// 26.7 -> 25.5 ms, 16: 32.4 -> 31.2, 256: 34.5 -> 32.9, 768: 42.4 -> 37.7
+// (profiles/r05f2/ldst_small.log); at 4096 blocks it needs 5.3 rounds (200 vs 70 ms, profiles/r05n)
 struct GtsSharedL : GtsShared {
+    static constexpr int kWavesPerSimd = 1;
     uint16_t tab[16384];
 };
 constexpr uint32_t kLdsTableMaxBlocks = 768;
@@ -532,7 +516,6 @@ __device__ int64_t compress_block_gts(const CompJob& j, SH& F, int32_t* T, int l
     int32_t i = 0, anchor = 0;
     uint32_t c = 67;
     int32_t S = 0;                       // step of the last hit (0: in a miss chain): the speculated probe distance
-    const int kmax = kSpecK;
     // accepted sequences not emitted yet (lanes 0 .. npend-1: probe, candidate, match end),
     // emitted while the next batch's table reads are in flight
     int npend = 0;
@@ -570,7 +553,7 @@ __device__ int64_t compress_block_gts(const CompJob& j, SH& F, int32_t* T, int l
     auto emit_pending = [&](uint32_t litv) {
         for (int k = 0; k < npend; ++k) {
             const int32_t pm = lane_val(pd_p, k), cm = lane_val(pd_c, k), e = lane_val(pd_e, k);
-            emit_seq(F, o, j, lane, anchor, pm, (uint32_t)(pm - cm), e - pm - 4, nullptr, true, litv);
+            emit_seq<SH, SrcG>(F, o, j, lane, anchor, pm, (uint32_t)(pm - cm), e - pm - 4, nullptr, true, litv);
             anchor = e;
         }
         npend = 0;
@@ -618,7 +601,7 @@ __device__ int64_t compress_block_gts(const CompJob& j, SH& F, int32_t* T, int l
             if (!(need && inw)) v = 0;
         }
         if (__ballot(need && !inw)) {   // (waited for here, not where the paths join: that wait would
-            if (need && !inw) v = ld_u32o(j, n32, x);   // also cover the previous batch's table stores)
+            if (need && !inw) v = ld_u32(j, x);   // also cover the previous batch's table stores)
             wait_vmem();
         }
         settle32(v);
@@ -627,8 +610,8 @@ __device__ int64_t compress_block_gts(const CompJob& j, SH& F, int32_t* T, int l
     // window refill at base b: loads issued now (with a round trip's other loads), written after its wait
     uint4 r0 = make_uint4(0, 0, 0, 0), r1 = r0;
     auto refill_issue = [&](int32_t b) {
-        r0 = ld16o(j, n32, b + 16 * lane);
-        r1 = ld16o(j, n32, b + 1024 + 16 * lane);
+        r0 = ld16(j, b + 16 * lane);
+        r1 = ld16(j, b + 1024 + 16 * lane);
     };
     auto refill_write = [&](int32_t b) {
         settle32(r0.x); settle32(r0.y); settle32(r0.z); settle32(r0.w);
@@ -646,7 +629,7 @@ __device__ int64_t compress_block_gts(const CompJob& j, SH& F, int32_t* T, int l
             {
                 const int32_t lim = min(mflimit - 1, ((g + 1) << 15) - 1) - i;   // same epoch, before mflimit
                 // (a division only near an epoch or block end: it is ~30 instructions on the chain)
-                K = lim >= (kmax - 1) * S ? kmax : 1 + lim / S;
+                K = lim >= (kSpecK - 1) * S ? kSpecK : 1 + lim / S;
             }
             const bool act = lane < K;
             const int32_t p = i + lane * S;
@@ -708,8 +691,8 @@ __device__ int64_t compress_block_gts(const CompJob& j, SH& F, int32_t* T, int l
                 __builtin_memcpy(&xa, j.src + pa + 16 * gt, 16);
                 __builtin_memcpy(&xb, j.src + pb + 16 * gt, 16);
             } else if (gk < K) {
-                xa = ld16o(j, n32, i + gk * S + 16 * gt);
-                if (gc >= 0) xb = ld16o(j, n32, gc + 16 * gt);
+                xa = ld16(j, i + gk * S + 16 * gt);
+                if (gc >= 0) xb = ld16(j, gc + 16 * gt);
             }
             const bool rf = (uint32_t)(i - wb) > 768u;          // the next batches' probes: window ahead
             if (rf) refill_issue(i);
@@ -722,7 +705,7 @@ __device__ int64_t compress_block_gts(const CompJob& j, SH& F, int32_t* T, int l
             // lane k < K: bytes equal at probe k (m, 128 = the whole window)
             const uint32_t gm = (uint32_t)(mm >> (8 * (lane & 7))) & 0xFFu;
             const int ft = gm ? __builtin_ctz(gm) : 0;
-            const uint32_t lmv = first_val(lm, mm, lane, ft);
+            const uint32_t lmv = first_val(lm, lane, ft);
             const int32_t m = gm ? 16 * ft + (int32_t)lmv : kSpecW;
             const bool hit = act && cand >= 0 && m >= 4;
             const bool lng = hit && m >= kSpecW && p + kSpecW < matchlimit;
@@ -801,7 +784,7 @@ __device__ int64_t compress_block_gts(const CompJob& j, SH& F, int32_t* T, int l
             mc = gt16_decode(T16[mh], gt_code_of(F, mh), g);
             if (mc < 0 || pm_ - mc < 1 || pm_ - mc > 65535) mc = -1;
         }
-        const uint32_t vw = mc >= 0 ? ld_u32o(j, n32, mc) : 0u;
+        const uint32_t vw = mc >= 0 ? ld_u32(j, mc) : 0u;
         const int32_t inext = lane_val(pm_ + (int32_t)step, nb - 1);   // where a batch without a hit goes on
         const bool rf = (uint32_t)(i - wb) > 512u;              // the window for what follows either way
         if (rf) refill_issue(i);
@@ -833,7 +816,7 @@ __device__ int64_t compress_block_gts(const CompJob& j, SH& F, int32_t* T, int l
         for (int k = 0; k < 12; ++k) atomicAdd(&g_cprof[k], (unsigned long long)cprof[k]);
 #endif
     if (npend) emit_pending(load_lit());
-    o = emit_tail(F, o, j, lane, anchor, n - anchor, nullptr);
+    o = emit_tail<SH, SrcG>(F, o, j, lane, anchor, n - anchor, nullptr);
     ring_flush(F, o, lane);
     for (int64_t t = o.flushed + lane; t < o.op; t += kWave) j.dst[t] = F.ring[t & RING_MASK(F)];
     return o.op;
@@ -846,7 +829,7 @@ __device__ unsigned int g_ctl_id[2 * kCtlMax];      // per block: HW_ID, XCC_ID
 #endif
 
 template <class SH>
-__global__ __launch_bounds__(64, 4) void lz4mi_compress_gts_kernel(CompArgs a, int32_t* tables) {
+__global__ __launch_bounds__(64, SH::kWavesPerSimd) void lz4mi_compress_gts_kernel(CompArgs a, int32_t* tables) {
     __shared__ SH F;
     const uint32_t b = blockIdx.x;
     if (b >= a.nblocks) return;
@@ -879,7 +862,6 @@ __global__ __launch_bounds__(64, 4) void lz4mi_compress_gts_kernel(CompArgs a, i
 #endif
 }
 
-
 // ---------------------------------------------------------------------------
 // Dependent blocks (the reference's LZ4.compress default, bufferCompress.js:182-236): the
 // blocks of one frame in order with one hash table carried from block to block (the
@@ -895,7 +877,6 @@ struct ChainShared {
     uint8_t slot[1024];   // batch duplicate-hash detection: lane ids keyed by hash & 1023
 };
 __shared__ int32_t g_ctab[16384];
-
 
 // The dependent-block chain with compress_block_gts's batching (round 3): hit batches of up to
 // kSpecK probes of one step, miss batches starting at the probe itself with the exact duplicate
@@ -942,7 +923,7 @@ __device__ int64_t match_extent_ring(const CompJob& j, const Ring& r, int lane, 
     return 4 * kWave + match_extent(j, lane, a + 4 * kWave, b + 4 * kWave, lim - 4 * kWave);
 }
 
-__device__ int64_t compress_block_chain2(const CompJob& j, ChainShared& F, int lane, Ring& r) {
+__device__ int64_t compress_block_chain(const CompJob& j, ChainShared& F, int lane, Ring& r) {
     int32_t* T = g_ctab;
     const int32_t start = j.start, end = j.start + j.len;
     const int32_t mflimit = end - 12, matchlimit = end - 5;
@@ -950,7 +931,6 @@ __device__ int64_t compress_block_chain2(const CompJob& j, ChainShared& F, int l
     int32_t i = start, anchor = start;
     uint32_t c = 67;
     int32_t S = 0;
-    const int kmax = kSpecK;
     int npend = 0;
     int32_t pd_p = 0, pd_c = 0, pd_e = 0;
     auto emit_pending = [&](uint32_t litv) {
@@ -990,7 +970,7 @@ __device__ int64_t compress_block_chain2(const CompJob& j, ChainShared& F, int l
         if (r.hi - i < kRingAhead) ring_advance(j, r, lane, i);
         if (c == 67 && S > 0) {
             // ================= hit batch
-            int K = __popcll(__ballot(lane < kmax && lane * S <= mflimit - 1 - i));
+            int K = __popcll(__ballot(lane < kSpecK && lane * S <= mflimit - 1 - i));
             const bool act = lane < K;
             const int32_t p = i + lane * S;
             const uint32_t seq = act ? rr32(j, r, p) : 0u;
@@ -1026,7 +1006,7 @@ __device__ int64_t compress_block_chain2(const CompJob& j, ChainShared& F, int l
             const uint64_t mm = __ballot(lm < 16);
             const uint32_t gm = (uint32_t)(mm >> (8 * (lane & 7))) & 0xFFu;
             const int ft = gm ? __builtin_ctz(gm) : 0;
-            const uint32_t lmv = first_val(lm, mm, lane, ft);
+            const uint32_t lmv = first_val(lm, lane, ft);
             const int32_t m = gm ? 16 * ft + (int32_t)lmv : kSpecW;
             const bool hit = act && cand >= 0 && m >= 4;
             const bool lng = hit && m >= kSpecW && p + kSpecW < matchlimit;
@@ -1150,7 +1130,7 @@ __global__ __launch_bounds__(64) void lz4mi_compress_chain_kernel(ChainArgs a) {
         const int32_t n = (int32_t)(rest < a.bsize ? rest : a.bsize);
         CompJob j{a.src, a.src_total, (int32_t)s0, n, a.out + a.out_off[b],
                   (uint64_t)n + (uint64_t)n / 255u + 16u, 0, nullptr};
-        const int64_t w = compress_block_chain2(j, F, lane, r);
+        const int64_t w = compress_block_chain(j, F, lane, r);
         if (lane == 0) a.comp_len[b] = (uint32_t)w;
     }
     __syncthreads();
@@ -1193,7 +1173,7 @@ __global__ __launch_bounds__(64) void lz4mi_compress_chains_kernel(ChainsArgs a)
         const uint32_t n = fe::chain_len(size, bmax, b);
         const uint64_t slot = a.blk_work_off[first + b];
         CompJob j{src, size, (int32_t)(b * bmax), (int32_t)n, a.work + slot, (uint64_t)n + n / 255u + 16u, 0, nullptr};
-        const int64_t w = compress_block_chain2(j, F, lane, r);
+        const int64_t w = compress_block_chain(j, F, lane, r);
         if (lane == 0) {
             a.comp_len[first + b] = (uint32_t)w;
             a.enc_off[first + b] = slot;
@@ -1227,8 +1207,8 @@ extern "C" hipError_t lz4mi_launch_compress(const uint8_t* in, const uint64_t* i
     lz4mi::CompArgs a{};
     a.in = in; a.in_off = in_off; a.in_len = in_len; a.out = out; a.out_off = out_off; a.out_len = out_len;
     a.nblocks = nblocks;
-    // speculative hit-chain batch encoder, 16 blocks per CU; `tables` = per-block scratch
-    if (nblocks <= lz4mi::kLdsTableMaxBlocks)   // one resident round at 3 blocks per CU: the table in LDS
+    // speculative hit-chain batch encoder; `tables` = per-block scratch
+    if (nblocks <= lz4mi::kLdsTableMaxBlocks)   // one resident round with the table in LDS (blocks per CU: at GtsShared)
         hipLaunchKernelGGL(lz4mi::lz4mi_compress_gts_kernel<lz4mi::GtsSharedL>, dim3(nblocks), dim3(64), 0, stream,
                            a, tables);
     else

@@ -1,6 +1,6 @@
 """The encoder shapes of tests/enc_shapes_common.py on the GPU: the batch encoder with its table in
 LDS and in global memory (compress_block_gts), through host and device pointers, and the chain kernel
-(compress_block_chain2) behind lz4mi_compress_chain and lz4mi_compress_block_table. Every comparison
+(compress_block_chain) behind lz4mi_compress_chain and lz4mi_compress_block_table. Every comparison
 is bit-exact against the CPU oracle (pinned to the reference on these very cases by
 tests/test_enc_shapes_cpu.py::test_reference_pin); there are no tolerances. What each family reaches in
 the kernels is in the common module's docstring and claims.
