@@ -428,11 +428,12 @@ __device__ __forceinline__ Run shfl_run(const Run& R, int l) {
 __device__ __forceinline__ Run match_run(const Ctx& c, int32_t ms, int32_t off, int32_t ml) {
     Run M{ms, 0, ms - off, off < ml ? off : 0, R_HIST};
     if (ml == 0 || ms >= c.cap) return M;
-    M.n = (ms + ml > c.cap ? c.cap : ms + ml) - ms;
+    // (ms < cap <= 2^31 - 1: the room cap - ms is compared, never the sum ms + ml, which leaves int32 near the top)
+    M.n = ml > c.cap - ms ? c.cap - ms : ml;
     // byte-wise: a dictionary source, a periodic source within 16 bytes of the
     // buffer start (its two-window pieces would read below it), or an output end
     // within 16 bytes (a plain source's 16-byte pieces stay inside [src, src + n))
-    if (c.out_off + M.src < 0 || (M.period && c.out_off + M.src < 16) || ms + 16 > c.cap) M.kind = R_BYTES;
+    if (c.out_off + M.src < 0 || (M.period && c.out_off + M.src < 16) || c.cap - ms < 16) M.kind = R_BYTES;
     return M;
 }
 // One past the last output byte a match run reads.
@@ -668,7 +669,17 @@ struct WaveGen {
 // SeqInfo::rsrc (t_seq .w) of a sequence whose match source was mapped to finished output:
 // the source + kMemoBase when the whole match was mapped (remap_src follows it in one step for
 // later rows), + kSplitBase when only its part after a literal prefix was (0: not mapped).
-constexpr int32_t kMemoBase = 0x40000000, kSplitBase = 0x20000000;
+// The sums are taken modulo 2^32; a mapped source rs lies in [-65536, 2^31). remap_src takes a
+// value for a whole-match memo only inside [kMemoLo, kMemoHi), i.e. for rs in [-65536, 2^27): a
+// whole-match value of a higher source lies above the window (from 2^30 on it wraps past 2^31),
+// and a split value lies in [kSplitBase - 65536, 2^32), above it for every rs -- both are
+// followed hop by hop, which is exact. (kSplitBase was 0x20000000: the split values of sources in
+// [2^29 - 65536, 2^29 + 2^27) lay inside the window and were followed as whole-match memos, to a
+// position 2^29 too low; tests/test_gpu_big_blocks.py.) piece_pipe subtracts the base its own
+// round chose (rbits, nlit_pack), never by the value's range.
+constexpr uint32_t kMemoBase = 0x40000000u, kSplitBase = 0x80000000u;
+constexpr uint32_t kMemoLo = kMemoBase - 65536u, kMemoHi = kMemoBase + (1u << 27);
+static_assert(kSplitBase - 65536u >= kMemoHi, "no split value inside the memo window");
 
 // A match source [rs, re) inside this table's output, mapped back through the
 // sequences that wrote it (out[y] = out[y - off] inside a match): 1 = it now
@@ -707,10 +718,10 @@ __device__ __forceinline__ int remap_src(const Ctx& c, const DecShared& S, uint3
             rs = ms;
         }
         if (re > ms + q.ml) return 0;
-        if (q.rsrc >= kMemoBase - 65536 && q.rsrc < kMemoBase + (1 << 27)) {
+        if ((uint32_t)q.rsrc - kMemoLo < kMemoHi - kMemoLo) {
             // sequence lo's match was itself mapped (by an earlier row) to finished output:
             // follow that mapping in one step instead of hop by hop
-            const int32_t base = q.rsrc - kMemoBase - ms;
+            const int32_t base = (int32_t)((uint32_t)q.rsrc - kMemoBase) - ms;
             rs += base;
             re += base;
             continue;
@@ -818,8 +829,8 @@ __device__ __forceinline__ void piece_pipe(const Ctx& c, DecShared& S, uint32_t 
                 const int32_t ms = q.out + q.ll;
                 const int32_t nl = i < 4 ? (int32_t)((nlit_pack >> (8 * i)) & 255u) : 0;   // split prefix
                 y = ms + nl;
-                n = (ms + q.ml > c.cap ? c.cap : ms + q.ml) - y;
-                src = (rbits >> i) & 1u ? q.rsrc - (nl ? kSplitBase : kMemoBase) : ms - q.off;
+                n = (q.ml > c.cap - ms ? c.cap : ms + q.ml) - y;   // (ms < cap: match_run)
+                src = (rbits >> i) & 1u ? (int32_t)((uint32_t)q.rsrc - (nl ? kSplitBase : kMemoBase)) : ms - q.off;
             }
             const uint32_t np = rd ? (uint32_t)(n + 15) >> 4 : 0u;
             const uint32_t incl = wave_incl_scan(np, lane);
@@ -1852,7 +1863,7 @@ __device__ __forceinline__ uint32_t round1(const Ctx& c, DecShared& S, int lane,
                 if (r == 1 || r == 3) {
                     M.src = rs;
                     if (c.out_off + rs < 16) M.kind = R_BYTES;
-                    S.t_seq[k].w = (uint32_t)(rs + (r == 3 ? kSplitBase : kMemoBase));
+                    S.t_seq[k].w = (uint32_t)rs + (r == 3 ? kSplitBase : kMemoBase);
                     rbits |= 1u << i;
                 } else if (r == 2) {
                     ML = Run{M.y, M.n, li, 0, R_LDS};
@@ -1908,7 +1919,7 @@ __device__ __forceinline__ void later_rounds(const Ctx& c, DecShared& S, int lan
                 const SeqInfo q = seq_info(S, k);
                 const int32_t ms = q.out + q.ll;
                 S.pms[idx] = (uint32_t)ms;
-                S.pme[idx] = (uint32_t)(ms + q.ml > c.cap ? c.cap : ms + q.ml);
+                S.pme[idx] = (uint32_t)(q.ml > c.cap - ms ? c.cap : ms + q.ml);   // (ms < cap: match_run)
             }
             np += (uint32_t)__popcll(bal);
         }

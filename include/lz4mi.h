@@ -121,7 +121,9 @@ extern "C" {
 #define LZ4MI_FRAMES_DECLINE_HASH_4G 10      /* LZ4MI_VERIFY_CONTENT and a result of 4 GiB or more */
 
 /* Largest block the kernels accept (the reference's largest block size is 4 MiB;
- * raw calls may pass more, up to 2^31-1 like the reference's `|0` arithmetic). */
+ * raw calls may pass more, up to 2^31-1 like the reference's `|0` arithmetic).
+ * The limit is exercised by tests/test_gpu_big_blocks.py: blocks of 128 MiB to 2^31-1
+ * bytes through the decoder and the size pass, blocks of up to 40 MiB through the encoder. */
 #define LZ4MI_MAX_BLOCK 0x7FFFFFFFu
 
 /* Worst-case compressed size of an n-byte block (n + n/255 + 16). */
