@@ -18,6 +18,7 @@
 #include <sys/mman.h>
 
 #include "../../include/lz4mi.h"
+#include "lz4mi_frames.h"
 #include "lz4mi_frames_enc.h"
 #include "lz4mi_launch.h"
 
@@ -1084,6 +1085,22 @@ int32_t lz4mi_frames_index(const uint8_t* in, const uint64_t* frame_off, const u
     int32_t* mstatus = (int32_t*)(msize + cap_blocks);
     LZ4MI_TRY(lz4mi_launch_frames_index(in, frame_off, frame_len, nframes, blk_in_off, blk_word, blk_frame, blk_size,
                                         cap_blocks, finfo, totals, meas_word, msize, mstatus, flags, s));
+    return LZ4MI_OK;
+}
+
+// The optional call between the two: two launches, no scratch, so no stream context and no lock.
+int32_t lz4mi_frames_verify_blocks(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len,
+                                   uint32_t nframes, const uint64_t* blk_in_off, const uint32_t* blk_word,
+                                   const uint32_t* blk_frame, uint32_t nblocks, int64_t* finfo, int32_t* blk_status,
+                                   uint32_t flags, void* stream) {
+    if (flags != LZ4MI_DEVICE_PTRS) return LZ4MI_ERR_ARG;
+    if (lz4mi::frames::verify_bad_args(in, frame_off, frame_len, nframes, blk_in_off, blk_word, blk_frame, nblocks,
+                                       finfo, blk_status))
+        return LZ4MI_ERR_ARG;
+    DeviceGuard dg;
+    if (dg.status()) return dg.status();
+    LZ4MI_TRY(lz4mi_launch_frames_verify(in, frame_off, frame_len, nframes, blk_in_off, blk_word, blk_frame, nblocks,
+                                         finfo, blk_status, pick_stream(stream)));
     return LZ4MI_OK;
 }
 

@@ -92,6 +92,36 @@ LZ4MI_HD uint64_t listed(const int64_t* fi) {
     return none ? 0 : (uint64_t)fi[kCount];
 }
 
+// lz4mi_frames_verify_blocks: is frame fi one whose block checksums the call checks -- no error yet, FLG 0x10,
+// blocks in the lists and all of them inside [0, nblocks)? Every decline that leaves the blocks listed
+// (MEASURE, SIZE_MISMATCH, UNSIZED_EXACT) is irrelevant here.
+LZ4MI_HD bool verify_checked(const int64_t* fi, uint32_t nblocks) {
+    if (fi[kErr] || !(fi[kHead] & 0x10)) return false;
+    const uint64_t n = listed(fi), first = (uint64_t)fi[kFirst];
+    return n != 0 && first <= nblocks && n <= nblocks - first;
+}
+// Is the record at `at` (absolute in `in`) -- a payload of n bytes, n < 2^31, and the LE32 behind it -- whole
+// inside the frame in[off .. off + len)? Differences only, so nothing wraps.
+LZ4MI_HD bool record_whole(uint64_t at, uint64_t n, uint64_t off, uint64_t len) {
+    return at >= off && at - off <= len && n + 4 <= len - (at - off);
+}
+
+// The argument rules of lz4mi_frames_verify_blocks and its host twin, behind the flags: the pointers a count needs,
+// and neither array the call writes may be an array it reads or the other one (the pointers themselves).
+inline bool verify_bad_args(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len, uint32_t nframes,
+                            const uint64_t* blk_in_off, const uint32_t* blk_word, const uint32_t* blk_frame,
+                            uint32_t nblocks, const int64_t* finfo, const int32_t* blk_status) {
+    if (nframes && (!finfo || !frame_off || !frame_len)) return true;
+    if (nblocks && (!in || !blk_in_off || !blk_word || !blk_frame || !blk_status)) return true;
+    const void* wr[2] = {finfo, blk_status};
+    const void* rd[6] = {in, frame_off, frame_len, blk_in_off, blk_word, blk_frame};
+    if (wr[0] && wr[0] == wr[1]) return true;
+    for (const void* w : wr)
+        for (const void* r : rd)
+            if (w && w == r) return true;
+    return false;
+}
+
 // Count pass of one frame.
 LZ4MI_HD void count_frame(const uint8_t* f, uint64_t len, int64_t* fi) {
     Walk w(f, len);

@@ -423,6 +423,44 @@ extern "C" int32_t lz4mi_host_frames_index(const uint8_t* in, const uint64_t* fr
     return LZ4MI_OK;
 }
 
+// lz4mi_frames_verify_blocks on the calling thread (include/lz4mi.h): the device call's two passes in their order
+// -- every status from finfo as it came in, then the fold -- with the same two rules (lz4mi_frames.h).
+extern "C" int32_t lz4mi_host_frames_verify_blocks(const uint8_t* in, const uint64_t* frame_off,
+                                                   const uint64_t* frame_len, uint32_t nframes,
+                                                   const uint64_t* blk_in_off, const uint32_t* blk_word,
+                                                   const uint32_t* blk_frame, uint32_t nblocks, int64_t* finfo,
+                                                   int32_t* blk_status, uint32_t flags) {
+    namespace fr = lz4mi::frames;
+    if (flags) return LZ4MI_ERR_ARG;
+    if (fr::verify_bad_args(in, frame_off, frame_len, nframes, blk_in_off, blk_word, blk_frame, nblocks, finfo,
+                            blk_status))
+        return LZ4MI_ERR_ARG;
+    if (nblocks == 0 || nframes == 0) return LZ4MI_OK;
+    for (uint32_t b = 0; b < nblocks; ++b) {
+        blk_status[b] = LZ4MI_OK;
+        const uint32_t f = blk_frame[b];
+        if (f >= nframes) continue;
+        const int64_t* fi = finfo + 8ull * f;
+        if (!fr::verify_checked(fi, nblocks) || b < (uint64_t)fi[fr::kFirst] ||
+            b - (uint64_t)fi[fr::kFirst] >= (uint64_t)fi[fr::kCount])
+            continue;
+        const uint64_t at = blk_in_off[b], n = blk_word[b] & 0x7FFFFFFFu;
+        uint32_t sum = 0;
+        const bool whole = fr::record_whole(at, n, frame_off[f], frame_len[f]);
+        if (whole) std::memcpy(&sum, in + at + n, 4);
+        if (!whole || lz4mi_xxh32(in + at, n, 0, LZ4MI_XXH_STANDARD) != sum) blk_status[b] = LZ4MI_ERR_BLOCK_CHECKSUM;
+    }
+    for (uint32_t f = 0; f < nframes; ++f) {
+        int64_t* fi = finfo + 8ull * f;
+        if (!fr::verify_checked(fi, nblocks)) continue;
+        const uint64_t first = (uint64_t)fi[fr::kFirst], n = (uint64_t)fi[fr::kCount];
+        bool bad = false;
+        for (uint64_t b = first; b < first + n; ++b) bad |= blk_status[b] != 0;
+        if (bad) fi[fr::kErr] = LZ4MI_ERR_BLOCK_CHECKSUM;
+    }
+    return LZ4MI_OK;
+}
+
 // lz4mi_frame_index on the calling thread (include/lz4mi.h): the function its kernel's one lane calls.
 extern "C" int32_t lz4mi_host_frame_index(const uint8_t* frame, uint64_t len, uint64_t* pay_off, uint32_t* size_word,
                                           uint32_t cap_blocks, int64_t* info) {

@@ -119,6 +119,12 @@ hipError_t lz4mi_launch_xxh32(const uint8_t* in, const uint64_t* off, const uint
                               hipStream_t stream);
 hipError_t lz4mi_launch_verify(const uint8_t* in, uint64_t in_total, const uint64_t* in_off, const uint32_t* in_len,
                                int32_t* status, uint32_t n, int frame_words, hipStream_t stream);
+// lz4mi_frames_verify_blocks: the block checksums of the checked frames into blk_status (one quad per listed block,
+// bounds per frame), then one wave per frame folds them into finfo[f][0]
+hipError_t lz4mi_launch_frames_verify(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len,
+                                      uint32_t nframes, const uint64_t* blk_in_off, const uint32_t* blk_word,
+                                      const uint32_t* blk_frame, uint32_t nblocks, int64_t* finfo, int32_t* blk_status,
+                                      hipStream_t stream);
 hipError_t lz4mi_launch_generate(uint8_t* out, uint32_t kind, uint32_t seed0, uint32_t bsize, uint32_t nblocks,
                                  hipStream_t stream);
 

@@ -12,6 +12,7 @@
 // rotl(rotl(rotl(rotl(v1,1)+v2,7)+v3,12)+v4,18)); `standard` selects the
 // XXH32 specification's rotl(v1,1)+rotl(v2,7)+rotl(v3,12)+rotl(v4,18).
 #include "lz4mi_common.h"
+#include "lz4mi_frames.h"
 #include "lz4mi_launch.h"
 
 namespace lz4mi {
@@ -167,6 +168,81 @@ __global__ __launch_bounds__(256) void lz4mi_verify_kernel(const uint8_t* in, ui
     status[buf] = st;
 }
 
+// Block checksums of a batch of frames checked in place (lz4mi_frames_verify_blocks): lz4mi_verify_kernel's
+// machine with per-frame bounds. The quad of block b looks up its frame f = blk_frame[b] and that frame's finfo
+// row: the record is checked when f < nframes, the frame is one the call checks (frames::verify_checked) and b lies
+// in the frame's own range of the lists -- entries behind totals[1] hold anything -- and it is whole when payload
+// and LE32 lie inside in[frame_off[f] .. +frame_len[f]). A cut record runs with length 0, reads nothing and is
+// LZ4MI_ERR_BLOCK_CHECKSUM; a record that is not checked runs with length 0 too and gets 0 (before the chain).
+// finfo is only read here: which records are checked cannot depend on another quad's verdict. The fold below
+// writes it.
+__global__ __launch_bounds__(256) void lz4mi_frames_verify_kernel(const uint8_t* in, const uint64_t* frame_off,
+                                                                  const uint64_t* frame_len, uint32_t nframes,
+                                                                  const uint64_t* blk_in_off, const uint32_t* blk_word,
+                                                                  const uint32_t* blk_frame, uint32_t nblocks,
+                                                                  const int64_t* finfo, int32_t* blk_status) {
+    const uint32_t buf = blockIdx.x * (blockDim.x >> 2) + (threadIdx.x >> 2);   // (no thread index: 4 nblocks may pass 2^32)
+    const int j = threadIdx.x & 3;
+    const bool live = buf < nblocks;   // (uniform per quad, like everything up to the chain)
+    const uint32_t f = live ? blk_frame[buf] : ~0u;
+    bool checked = false, whole = false;
+    uint64_t at = 0;
+    uint32_t want = 0;
+    if (live && f < nframes) {
+        const int64_t* fi = finfo + 8ull * f;
+        checked = frames::verify_checked(fi, nblocks) && buf >= (uint64_t)fi[frames::kFirst] &&
+                  buf - (uint64_t)fi[frames::kFirst] < (uint64_t)fi[frames::kCount];
+        if (checked) {
+            at = blk_in_off[buf];
+            want = blk_word[buf] & 0x7FFFFFFFu;
+            whole = frames::record_whole(at, want, frame_off[f], frame_len[f]);
+        }
+    }
+    // A record that is not checked gets its 0 here and is no block from now on: `checked` as one more value that
+    // lives through the chain would cost the third wave per SIMD (170 VGPRs against lz4mi_verify_kernel's 168).
+    if (live && !checked && j == 0) blk_status[buf] = 0;
+    const bool rec = live && checked;
+    const uint8_t* p = whole ? in + at : nullptr;   // (nullptr: a cut record, or no record; with L = 0 never read)
+    const uint64_t L = whole ? want : 0;   // (64 bits: the chain loop's schedule, as in lz4mi_verify_kernel)
+    const uint64_t stripes = L >= 16 ? L / 16 : 0;
+
+    constexpr uint32_t seed = 0;
+    uint32_t init[4] = { seed + P1 + P2, seed + P2, seed, seed - P1 };
+    const uint32_t v = stripe_chain(init[j], p + 4 * j, stripes, [](const uint8_t* a) {
+        uint32_t w;
+        __builtin_memcpy(&w, a, 4);
+        return w;
+    });
+
+    const int lane = threadIdx.x & 63, qb = lane & ~3;
+    uint32_t v1 = __shfl(v, qb + 0, 64), v2 = __shfl(v, qb + 1, 64), v3 = __shfl(v, qb + 2, 64),
+             v4 = __shfl(v, qb + 3, 64);
+    if (!rec || j != 0) return;
+    int32_t st = kErrBlockChecksum;
+    if (p) {
+        const uint32_t h = finish(v1, v2, v3, v4, p, L, seed, 1);
+        if (h == load_le32(p + L, false)) st = 0;
+    }
+    blk_status[buf] = st;
+}
+
+// The fold of lz4mi_frames_verify_blocks: one wave per frame over the statuses of its blocks, like the finish
+// pass of the decode. A checked frame with a failing record gets finfo[f][0] = LZ4MI_ERR_BLOCK_CHECKSUM, by one
+// plain store of lane 0; no other word of finfo is written, and a frame that is not checked (its [0] was set
+// before the call, for one) is not touched. The result is a function of blk_status alone.
+__global__ __launch_bounds__(64) void lz4mi_frames_verify_fold_kernel(int64_t* finfo, uint32_t nframes,
+                                                                      uint32_t nblocks, const int32_t* blk_status) {
+    const uint32_t f = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (f >= nframes) return;
+    int64_t* fi = finfo + 8ull * f;
+    if (!frames::verify_checked(fi, nblocks)) return;
+    const uint64_t first = (uint64_t)fi[frames::kFirst], n = (uint64_t)fi[frames::kCount];
+    bool bad = false;
+    for (uint64_t k = lane; k < n; k += 64) bad |= blk_status[first + k] != 0;
+    if (__ballot(bad) && lane == 0) fi[frames::kErr] = kErrBlockChecksum;
+}
+
 // ---------------------------------------------------------------------------
 // Synthetic block generator (identical to oracle/lz4_oracle.c
 // orc_generate for kinds 0..2). One wave per block; the serial xorshift32
@@ -248,6 +324,21 @@ extern "C" hipError_t lz4mi_launch_verify(const uint8_t* in, uint64_t in_total, 
     // as lz4mi_launch_xxh32: one wave (16 blocks) per workgroup
     hipLaunchKernelGGL(lz4mi::lz4mi_verify_kernel, dim3((n * 4 + 63) / 64), dim3(64), 0, stream, in, in_total, in_off,
                        in_len, status, n, frame_words);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t lz4mi_launch_frames_verify(const uint8_t* in, const uint64_t* frame_off,
+                                                 const uint64_t* frame_len, uint32_t nframes,
+                                                 const uint64_t* blk_in_off, const uint32_t* blk_word,
+                                                 const uint32_t* blk_frame, uint32_t nblocks, int64_t* finfo,
+                                                 int32_t* blk_status, hipStream_t stream) {
+    if (nblocks == 0 || nframes == 0) return hipSuccess;
+    // as lz4mi_launch_verify: one wave (16 blocks) per workgroup; 64-bit: nblocks * 4 may pass 2^32
+    const uint32_t groups = (uint32_t)(((uint64_t)nblocks * 4 + 63) / 64);
+    hipLaunchKernelGGL(lz4mi::lz4mi_frames_verify_kernel, dim3(groups), dim3(64), 0, stream, in, frame_off, frame_len,
+                       nframes, blk_in_off, blk_word, blk_frame, nblocks, finfo, blk_status);
+    hipLaunchKernelGGL(lz4mi::lz4mi_frames_verify_fold_kernel, dim3(nframes), dim3(64), 0, stream, finfo, nframes,
+                       nblocks, blk_status);
     return hipGetLastError();
 }
 

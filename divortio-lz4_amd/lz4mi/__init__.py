@@ -61,7 +61,8 @@ EXPORTS = ("lz4mi_status_message", "lz4mi_init", "lz4mi_device_count", "lz4mi_ve
            "lz4mi_decoded_sizes", "lz4mi_host_decoded_size", "lz4mi_host_block_read_end",
            "lz4mi_verify_blocks", "lz4mi_host_verify_blocks", "lz4mi_frames_index", "lz4mi_frames_decompress",
            "lz4mi_host_frames_index", "lz4mi_host_frame_index", "lz4mi_frame_bound", "lz4mi_frames_plan",
-           "lz4mi_frames_compress", "lz4mi_host_frames_plan", "lz4mi_host_frames_compress")
+           "lz4mi_frames_compress", "lz4mi_host_frames_plan", "lz4mi_host_frames_compress",
+           "lz4mi_frames_verify_blocks", "lz4mi_host_frames_verify_blocks")
 
 
 class Lz4miError(RuntimeError):
@@ -146,6 +147,11 @@ def lib():
         L.lz4mi_frames_decompress.restype = ctypes.c_int32
         L.lz4mi_frames_decompress.argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _vp,
                                               _vp, ctypes.c_uint32, _vp]
+        fverify = [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32]
+        L.lz4mi_frames_verify_blocks.restype = ctypes.c_int32
+        L.lz4mi_frames_verify_blocks.argtypes = fverify + [_vp]
+        L.lz4mi_host_frames_verify_blocks.restype = ctypes.c_int32
+        L.lz4mi_host_frames_verify_blocks.argtypes = fverify
         L.lz4mi_host_frames_index.restype = ctypes.c_int32
         L.lz4mi_host_frames_index.argtypes = [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp,
                                               _vp, ctypes.c_uint32]
@@ -517,6 +523,25 @@ def host_frames_index(arena, frame_off, frame_len, cap_blocks, measure=False, js
     return res
 
 
+def host_frames_verify_blocks(arena, frame_off, frame_len, index):
+    """lz4mi_frames_verify_blocks on the calling thread (lz4mi_host_frames_verify_blocks, no device needed): the
+    block checksums of the frames host_frames_index listed (`index`: its dict; nblocks is the lists' length).
+    index["finfo"] is updated in place -- [0] of a checked frame with a failing record becomes
+    ERR_BLOCK_CHECKSUM -- and blk_status (int32 per list entry: 0 or ERR_BLOCK_CHECKSUM) is returned."""
+    a = _u8(arena)
+    off = np.ascontiguousarray(frame_off, dtype=np.uint64)
+    ln = np.ascontiguousarray(frame_len, dtype=np.uint64)
+    fi = index["finfo"]
+    assert off.ndim == 1 and off.shape == ln.shape and fi.shape == (off.size, 8)
+    assert fi.dtype == np.int64 and fi.flags.c_contiguous
+    nb = index["blk_in_off"].size
+    status = np.zeros(nb, dtype=np.int32)
+    _check(lib().lz4mi_host_frames_verify_blocks(_p(a) if a.size else np.zeros(1, dtype=np.uint8).ctypes.data, _p(off),
+                                                 _p(ln), off.size, _p(index["blk_in_off"]), _p(index["blk_word"]),
+                                                 _p(index["blk_frame"]), nb, _p(fi), _p(status), 0))
+    return status
+
+
 def host_frame_index(frame, pay_off, size_word, cap_blocks, info):
     """lz4mi_frame_index on the calling thread (lz4mi_host_frame_index, no device needed) into the caller's
     arrays: pay_off (uint64) and size_word (uint32), of which the first cap_blocks entries may be written, and
@@ -649,6 +674,17 @@ def frames_index_dev(in_ptr, frame_off_ptr, frame_len_ptr, nframes, blk_in_off_p
                                     blk_frame_ptr, blk_size_ptr, cap_blocks, finfo_ptr, totals_ptr,
                                     DEVICE_PTRS | (FRAMES_MEASURE if measure else 0) | (JS_EXACT if js_exact else 0),
                                     stream or None))
+
+
+def frames_verify_blocks_dev(in_ptr, frame_off_ptr, frame_len_ptr, nframes, blk_in_off_ptr, blk_word_ptr, blk_frame_ptr,
+                             nblocks, finfo_ptr, blk_status_ptr, stream=0):
+    """Block checksums of the frames lz4mi_frames_index listed (include/lz4mi.h lz4mi_frames_verify_blocks): device
+    pointers, asynchronous on `stream`, nothing read back. blk_status holds 0 or ERR_BLOCK_CHECKSUM per list entry
+    afterwards, and finfo[f][0] of a frame with a failing record ERR_BLOCK_CHECKSUM, so frames_decompress_dev
+    passes it over."""
+    _check(lib().lz4mi_frames_verify_blocks(in_ptr, frame_off_ptr, frame_len_ptr, nframes, blk_in_off_ptr, blk_word_ptr,
+                                            blk_frame_ptr, nblocks, finfo_ptr, blk_status_ptr, DEVICE_PTRS,
+                                            stream or None))
 
 
 def frames_decompress_dev(in_ptr, blk_in_off_ptr, blk_word_ptr, blk_frame_ptr, blk_size_ptr, nblocks, finfo_ptr,

@@ -1138,7 +1138,8 @@ def decompress_frame_host(frame, js_exact=False, verify_checksum=True, verify_bl
 
 
 def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measure=False, stream=None, report=None,
-                             return_errors=False, offsets=None, lengths=None, cap_blocks=None, chains=False):
+                             return_errors=False, offsets=None, lengths=None, cap_blocks=None, chains=False,
+                             verify_blocks=False):
     """Decode a batch of device-resident frames with one index call, one output allocation and one decode
     call (lz4mi_frames_index / lz4mi_frames_decompress): the frames' size words are walked in parallel, one
     lane per frame, the blocks of all frames decoded by one batch launch, and with verify_checksum the
@@ -1153,6 +1154,13 @@ def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measu
     by default for anything longer than one block; with js_exact also an independent frame whose tail rewrite
     reads below a block) is decoded in the same call, one wave per frame in block order, instead of being
     declined: right for many frames, slow for a few long ones (one wave walks the whole frame).
+    verify_blocks: the block checksums (FLG 0x10) of all frames are checked on the device, one quad of lanes per
+    record (lz4mi_frames_verify_blocks), enqueued behind each index call and in front of its read-back, so no
+    synchronisation is added and the statuses come back with finfo. A frame with a failing record gets no room
+    in the output, is not decoded and is Lz4miError(ERR_BLOCK_CHECKSUM) with route "batch" -- before any block's
+    own error and the content checksum, as decompress_frame_device(verify_blocks=True) reports it; a frame the
+    batch declines goes to that call with verify_blocks. report["bad_block"][f] is then the index, within
+    the frame, of the first failing record of a frame whose blocks were listed, else None.
     Two host synchronisations: finfo and totals read back after the index (a third when cap_blocks -- the
     guess of _decode_measured, or the caller's -- was too small and the index runs again with the exact
     need), and finfo after the decode. A frame the batch declines (finfo[f][7], include/lz4mi.h
@@ -1179,6 +1187,8 @@ def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measu
     if report is None:
         report = {}
     report.update(routes=[None] * nf, declined=[0] * nf, index_calls=0)
+    if verify_blocks:
+        report["bad_block"] = [None] * nf
     if nf == 0:
         return []
     lz4mi.init(dev.index if dev.index is not None else torch.cuda.current_device())
@@ -1196,11 +1206,17 @@ def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measu
             cap = max(1, int(cap))
             blk_in_off = torch.empty(cap, dtype=torch.int64, device=dev)
             blk32 = torch.empty((3, cap), dtype=torch.int32, device=dev)   # word, frame, size
-            fin = torch.zeros(8 * nf + 4, dtype=torch.int64, device=dev)   # finfo, then totals
+            # finfo, then totals; with verify_blocks the int32 statuses of the cap list entries behind them, so
+            # that one copy brings everything back
+            fin = torch.zeros(8 * nf + 4 + ((cap + 1) // 2 if verify_blocks else 0), dtype=torch.int64, device=dev)
             lz4mi.frames_index_dev(arena.data_ptr(), span[0].data_ptr(), span[1].data_ptr(), nf, blk_in_off.data_ptr(),
                                    blk32[0].data_ptr(), blk32[1].data_ptr(), blk32[2].data_ptr(), cap, fin.data_ptr(),
                                    fin.data_ptr() + 64 * nf, s.cuda_stream, measure=measure, js_exact=js_exact)
             report["index_calls"] += 1
+            if verify_blocks:
+                lz4mi.frames_verify_blocks_dev(arena.data_ptr(), span[0].data_ptr(), span[1].data_ptr(), nf,
+                                               blk_in_off.data_ptr(), blk32[0].data_ptr(), blk32[1].data_ptr(), cap,
+                                               fin.data_ptr(), fin.data_ptr() + 8 * (8 * nf + 4), s.cuda_stream)
             h = fin.cpu().numpy()
             need = int(h[8 * nf])
             if need <= cap or report["index_calls"] > 1:
@@ -1208,6 +1224,12 @@ def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measu
             cap = need
         info = h[:8 * nf].reshape(nf, 8)
         listed = int(h[8 * nf + 1])     # the decode launch and its scratch take the blocks listed, not the guess
+        if verify_blocks:
+            blk_status = h[8 * nf + 4:].view(np.int32)
+            for f in range(nf):
+                if info[f, 0] == lz4mi.ERR_BLOCK_CHECKSUM:
+                    first = int(info[f, 4])
+                    report["bad_block"][f] = int(np.flatnonzero(blk_status[first:first + int(info[f, 6])])[0])
         # one allocation, the frames the call decodes at 16-byte-aligned offsets; a content size above the
         # bound sizes nothing: that frame gets no room, which declines it
         out_off, out_cap, at = [0] * nf, [0] * nf, 0
@@ -1234,7 +1256,7 @@ def decompress_frames_device(frames, js_exact=False, verify_checksum=True, measu
             r = {}
             try:
                 res[f] = decompress_frame_device(one, js_exact=js_exact, verify_checksum=verify_checksum, stream=stream,
-                                                 report=r)
+                                                 report=r, verify_blocks=verify_blocks)
             except lz4mi.Lz4miError as e:
                 err = e
             report["routes"][f] = r.get("route", "host")

@@ -523,7 +523,8 @@ int32_t lz4mi_frame_index(const uint8_t* frame, uint64_t len, uint64_t* pay_off,
  * finfo or `out` that is `in`, one of the lists, frame_out_off, frame_out_cap or the other of the two (the call
  * reads those while it writes these). LZ4MI_LINKED* and
  * LZ4MI_VERIFY_BLOCKS are not taken: a linked pass has no barrier at a frame's first slot, and the verify kernel
- * takes a single in_total; block checksums are skipped, and without LZ4MI_FRAMES_CHAINS frames with blocks that
+ * takes a single in_total; block checksums are skipped (lz4mi_frames_verify_blocks, below, checks them between the
+ * two calls, with bounds per frame), and without LZ4MI_FRAMES_CHAINS frames with blocks that
  * read the blocks before them are declined (DEPENDENT).
  * A block ends where its size word says: the bytes behind it read as 0, in the index call's measuring and in the
  * decode (the rule of lz4mi_decoded_sizes and lz4mi_decompress_blocks), with or without LZ4MI_FRAMES_CHAINS. The
@@ -546,6 +547,46 @@ int32_t lz4mi_frames_decompress(const uint8_t* in, const uint64_t* blk_in_off, c
                                 const uint32_t* blk_frame, const uint32_t* blk_size, uint32_t nblocks,
                                 int64_t* finfo, uint32_t nframes, uint8_t* out, const uint64_t* frame_out_off,
                                 const uint64_t* frame_out_cap, uint32_t flags, void* stream);
+/*
+ * lz4mi_frames_verify_blocks: the optional third call, between index and decompress -- the block checksums (FLG
+ * 0x10) of every frame of the batch checked on the device, one quad of lanes per record as in lz4mi_verify_blocks,
+ * with bounds per frame. Device pointers only (flags must be exactly LZ4MI_DEVICE_PTRS), asynchronous on `stream`,
+ * no scratch, nothing read back. It takes the lists and finfo as lz4mi_frames_index left them (nblocks = cap_blocks
+ * or totals[1]; totals is not passed and stays the index call's).
+ * Frame f is checked when finfo[f][0] == 0, finfo[f][1] & 0x10, it has blocks in the lists (no decline CAP_BLOCKS /
+ * PAST_END / EMPTY) and [4] + [6] <= nblocks. Every other decline is irrelevant: a frame declined as MEASURE,
+ * SIZE_MISMATCH or UNSIZED_EXACT has its blocks listed and is checked.
+ * For block b of a checked frame, b in [finfo[f][4], +finfo[f][6]) with blk_frame[b] == f, the record is the payload
+ * in[blk_in_off[b] .. +n), n = blk_word[b] & 0x7FFFFFFF (a stored block's raw bytes are a payload like any other),
+ * and the LE32 behind it: blk_status[b] = 0 when that word equals XXH32 (spec convergence, seed 0) of the payload,
+ * else LZ4MI_ERR_BLOCK_CHECKSUM. Nothing outside the frame's own range in[frame_off[f] .. +frame_len[f]) is read: a
+ * record with blk_in_off[b] < frame_off[f] or blk_in_off[b] + n + 4 > frame_off[f] + frame_len[f] (in 64-bit
+ * differences that cannot wrap) is LZ4MI_ERR_BLOCK_CHECKSUM without a byte of it being read -- whatever follows
+ * the frame in `in`. Every other entry of blk_status[0 .. nblocks) is set to 0: the blocks of frames that are not
+ * checked, a blk_frame[b] >= nframes, an entry that is in no checked frame's range.
+ * A checked frame with at least one failing record gets finfo[f][0] = LZ4MI_ERR_BLOCK_CHECKSUM, folded from
+ * blk_status by a second pass (one wave per frame), so the outcome does not depend on the order in which records
+ * finish, and a frame whose [0] was non-zero keeps its value. Nothing else of finfo changes.
+ * lz4mi_frames_decompress then passes such a frame over, as any frame in error, and writes no byte of `out` for it.
+ * That is lz4mi_frame_decompress's rule under LZ4MI_VERIFY_BLOCKS: header errors first (the index sets them, and
+ * such a frame is not checked), then any failing block checksum before every block's own error (a stored block's
+ * LZ4MI_ERR_RANGE included) and before the content checksum.
+ * Any flag but LZ4MI_DEVICE_PTRS, a NULL finfo / frame_off / frame_len with nframes > 0, a NULL in / list /
+ * blk_status with nblocks > 0, or a finfo or blk_status that is `in`, frame_off, frame_len, one of the lists or
+ * the other of the two: LZ4MI_ERR_ARG before the device is looked at. nblocks == 0 or nframes == 0: LZ4MI_OK,
+ * nothing is written.
+ * Footprint: blk_status[0 .. nblocks) and finfo[f][0] of the frames that fail; nothing else.
+ * lz4mi_host_frames_verify_blocks: the same contract on the calling thread (host pointers, no device needed, flags
+ * must be 0): the checker of the device pass.
+ */
+int32_t lz4mi_frames_verify_blocks(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len,
+                                   uint32_t nframes, const uint64_t* blk_in_off, const uint32_t* blk_word,
+                                   const uint32_t* blk_frame, uint32_t nblocks, int64_t* finfo /* nframes x 8 */,
+                                   int32_t* blk_status /* nblocks */, uint32_t flags, void* stream);
+int32_t lz4mi_host_frames_verify_blocks(const uint8_t* in, const uint64_t* frame_off, const uint64_t* frame_len,
+                                        uint32_t nframes, const uint64_t* blk_in_off, const uint32_t* blk_word,
+                                        const uint32_t* blk_frame, uint32_t nblocks, int64_t* finfo,
+                                        int32_t* blk_status, uint32_t flags);
 /*
  * lz4mi_frames_index on the calling thread (host pointers, no device needed; flags: LZ4MI_FRAMES_MEASURE |
  * LZ4MI_JS_EXACT): the checker of the device passes. Measuring is lz4mi_host_decoded_size over each block alone.
