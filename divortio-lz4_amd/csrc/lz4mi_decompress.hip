@@ -5,7 +5,8 @@
 // spec-valid input (positions absolute in `out`, dictionary below out[0],
 // clipped match writes, the four error strings). The reference's double-copy-
 // tail rewrite is reproduced in reference mode, LZ4MI_JS_EXACT, by
-// this kernel (DecArgs::f1check: the in-chunk replay, step 7) -- batches here,
+// this kernel (the in-chunk replay, step 7; the batch kernel has one instantiation
+// per mode, lz4mi_decompress_kernel / lz4mi_decompress_ref_kernel) -- batches here,
 // small batches through the export path (lz4mi_expand.hip), whose blocks with a
 // rewrite come back here (DecArgs::redo). Only LZ4MI_JS_COMPAT still decodes the
 // blocks in order on one lane (lz4mi_decompress_serial.hip).
@@ -45,10 +46,11 @@
 //     written with exact-width unaligned 16/8/4/2/1-byte pieces (the last
 //     16-byte piece of a run overlaps its predecessor instead of spilling),
 //     so lanes never touch each other's bytes:
-//       round 1: all literal runs (from LDS; those of >= 16 bytes, of any
-//                length, cut into 16-byte pieces that are dealt to the lanes,
-//                64 per store: LitDeal) and every match whose source lies
-//                entirely in output finished by earlier chunks;
+//       round 1: all literal runs (from LDS, in a pass of their own before the
+//                row loop; those of >= 16 bytes, of any length, cut into
+//                16-byte pieces that are dealt to the lanes, 64 per store:
+//                LitDeal) and every match whose source lies entirely in
+//                output finished by earlier chunks;
 //       round r: after the previous round's stores are complete, every
 //                pending match whose source range meets no pending match.
 //     The earliest pending match is always ready, so the rounds terminate;
@@ -1023,8 +1025,8 @@ __device__ __forceinline__ void short_literals(const Ctx& c, int32_t y, int32_t 
     if (n & 1) d[o] = (uint8_t)lo;
 }
 
-// Literal runs of >= 16 bytes from the staged chunk (R_LDS), piece-parallel like the matches of
-// piece_pipe: every run is cut into 16-byte pieces (the last one overlaps its predecessor, so
+// Literal runs from the staged chunk (R_LDS), piece-parallel like the matches of piece_pipe:
+// every run of >= 16 bytes is cut into 16-byte pieces (the last one overlaps its predecessor, so
 // no byte outside [y, y + n) is written) and the pieces of all listed runs are dealt to the
 // lanes in order, 64 per row; a lane does one stage16 and one out16 per row instead of every
 // lane going round as often as the row's longest run needs. The run list (rank -> {y, stage
@@ -1034,10 +1036,13 @@ __device__ __forceinline__ void short_literals(const Ctx& c, int32_t y, int32_t 
 // Two users: the chunk's own literal runs, once before round 1's loop (dealt_literals), and
 // round 1's remapped sources (a match mapped into a literal run, the literal prefix of a
 // split match), listed row by row and flushed when the list is full and after the loop.
+// A remapped source of under 16 bytes is listed too, as one piece of its exact width
+// (short_literals): round 1's row loop then holds no literal store at all.
 // Bounds: the literals of a table's sequences lie inside the window (else the sequence is
 // cut), so a chunk's own runs hold <= kLim bytes together, and each run of >= 16 bytes takes
 // >= 17 compressed bytes of a token starting in the chunk: all of them fit one list. A
-// remapped run is at most kLaneBytes long.
+// remapped run is at most kLaneBytes long, i.e. kLaneBytes / 16 pieces, and one of under 16
+// bytes is one piece: kLitRuns entries hold at most kLitRows * 64 pieces.
 constexpr int kLitRuns = 64;                                   // list entries
 constexpr int kLitRows = kLitRuns * (kLaneBytes / 16) / 64;    // bitmap rows
 static_assert((kChunk + 16) / 17 <= kLitRuns, "every run of >= 16 literal bytes of a chunk has a list entry");
@@ -1053,7 +1058,7 @@ struct LitDeal {
     static __device__ __forceinline__ uint64_t* bitmap(DecShared& S) {
         return reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(S.pms) + kLitRuns * sizeof(PEnt));
     }
-    // Lists the run {y, src, n >= 16} of every lane with `has` (bal = its ballot, not 0; at most
+    // Lists the run {y, src, n >= 1} of every lane with `has` (bal = its ballot, not 0; at most
     // kLitRuns - R lanes).
     __device__ __forceinline__ void add(DecShared& S, int lane, bool has, uint64_t bal, int32_t y, int32_t src, int32_t n) {
         if (R == 0) {
@@ -1086,10 +1091,14 @@ struct LitDeal {
             const uint32_t p = 64u * t + (uint32_t)lane;
             if (p < P) {
                 const PEnt e = L[r];
-                const int32_t d0 = 16 * ((int32_t)p - e.p0);
-                const int32_t d = d0 < e.n - 16 ? d0 : e.n - 16;
-                const uint4 v = stage16(S.stage, e.src + d);
-                if (LZ4MI_ABLATE != 4) out16(c.dst + e.y + d, v);
+                if (e.n < 16) {   // (a remapped source of round 1: its exact width)
+                    short_literals(c, e.y, e.n, stage16(S.stage, e.src));
+                } else {
+                    const int32_t d0 = 16 * ((int32_t)p - e.p0);
+                    const int32_t d = d0 < e.n - 16 ? d0 : e.n - 16;
+                    const uint4 v = stage16(S.stage, e.src + d);
+                    if (LZ4MI_ABLATE != 4) out16(c.dst + e.y + d, v);
+                }
             }
         }
         __syncthreads();   // the list may be rewritten, or S.pms reused (pat_round1)
@@ -1097,8 +1106,10 @@ struct LitDeal {
     }
 };
 
-// The chunk's own literal runs of >= 16 bytes. A chunk without one (text, copy) pays a ballot
-// per sequence row.
+// The chunk's own literal runs, all of them, before round 1's loop: those of >= 16 bytes listed
+// and dealt, the shorter ones written by their own lanes in 8/4/2/1-byte pieces behind one
+// ballot per row (a row of text, where all 64 lanes hold one, costs what it cost inside round
+// 1's loop). A row with neither pays the two ballots.
 __device__ __forceinline__ void dealt_literals(const Ctx& c, DecShared& S, int lane, uint32_t nseq) {
     LitDeal D;
     for (uint32_t i = 0; 64 * i < nseq; ++i) {
@@ -1106,9 +1117,12 @@ __device__ __forceinline__ void dealt_literals(const Ctx& c, DecShared& S, int l
         const uint4& e = S.t_seq[k < nseq ? k : 0u];
         const uint32_t y = e.x, lw = e.y;
         const uint32_t n = k < nseq ? lw >> 16 : 0u;
-        const bool has = n >= 16;
+        const bool has = n >= 16, shortL = n > 0 && n < 16;
         const uint64_t bal = __ballot(has);
         if (bal) D.add(S, lane, has, bal, (int32_t)y, (int32_t)(lw & 0xFFFFu), (int32_t)n);
+        if (__ballot(shortL)) {
+            if (shortL) short_literals(c, (int32_t)y, (int32_t)n, stage16(S.stage, (int32_t)(lw & 0xFFFFu)));
+        }
     }
     D.flush(c, S, lane);
 }
@@ -1819,9 +1833,10 @@ __device__ __forceinline__ uint32_t source_map(const Ctx& c, DecShared& S, int l
     return msh;
 }
 
-// Round 1: all literal runs (from LDS) and every match whose source lies, or maps back to,
-// output finished by earlier chunks. Returns the pending matches: bit i = that of
-// sequence 64 i + lane.
+// Round 1: all literal runs (from LDS: the chunk's own before the row loop, dealt_literals) and
+// every match whose source lies, or maps back to, output finished by earlier chunks. The row
+// loop holds match planning, the remap and the listing of remapped literal sources only.
+// Returns the pending matches: bit i = that of sequence 64 i + lane.
 __device__ __forceinline__ uint32_t round1(const Ctx& c, DecShared& S, int lane, uint32_t nseq, uint32_t msh, Prof& prof) {
     uint32_t pend = 0;    // bit i: the match of sequence 64i+lane is still to be written
     uint32_t ready = 0;   // bit i: ... is written by this lane in this round
@@ -1832,15 +1847,7 @@ __device__ __forceinline__ uint32_t round1(const Ctx& c, DecShared& S, int lane,
     for (uint32_t i = 0; 64 * i < nseq; ++i) {            // round 1
         const uint32_t k = 64 * i + lane;
         Run M = no_run(), ML = no_run();
-        SeqInfo q = seq_info(S, k < nseq ? k : 0u);
-        if (k >= nseq) q.ll = 0;
-        {   // the literal runs first (their registers are free before the remap)
-            // (runs of >= 16 bytes: dealt_literals, before this loop)
-            const bool shortL = q.ll > 0 && q.ll < 16;
-            if (__ballot(shortL)) {
-                if (shortL) short_literals(c, q.out, q.ll, stage16(S.stage, q.lit));
-            }
-        }
+        const SeqInfo q = seq_info(S, k < nseq ? k : 0u);   // (its literal run: dealt_literals, above)
         PROF(23);
         if (k < nseq) {
             const int32_t t0 = q.out;
@@ -1880,13 +1887,10 @@ __device__ __forceinline__ uint32_t round1(const Ctx& c, DecShared& S, int lane,
         if (M.kind != R_NONE && !longM && fastM) ready |= 1u << i;
         PROF(16);
         {
-            const bool dealML = ML.n >= 16 && !longML, shortML = ML.n > 0 && ML.n < 16;
+            const bool dealML = ML.n > 0 && !longML;   // (under 16 bytes too: one piece of its exact width)
             if (const uint64_t bal = __ballot(dealML)) {
                 if (D.R + (uint32_t)__popcll(bal) > (uint32_t)kLitRuns) D.flush(c, S, lane);
                 D.add(S, lane, dealML, bal, ML.y, ML.src, ML.n);
-            }
-            if (__ballot(shortML)) {
-                if (shortML) short_literals(c, ML.y, ML.n, stage16(S.stage, ML.src));
             }
         }
         PROF(17);
@@ -2021,9 +2025,13 @@ constexpr bool kParseOnly = LZ4MI_ABLATE == 2 || LZ4MI_ABLATE == 3;   // (timing
 // batch, lz4mi_decompress_frames_chain_kernel). Returns the status written to status[b] (0 where none is). The
 // three batch kernels take none of this: with CH = false the function compiles to what it was without it -- a
 // split into a wrapper and a per-block function did not (other register allocation, bench.py 0.7 % slower).
-template <bool XP, bool LK = false, bool CH = false>
+// F1: step 7 known at compile time (the batch kernel: one instantiation per decode mode, so the spec one holds
+// neither f1_table nor cut_match's rewrite branch), or DecArgs::f1check (the export and frame-chain kernels).
+constexpr int kF1Arg = -1, kF1Off = 0, kF1On = 1;
+template <bool XP, bool LK = false, bool CH = false, int F1 = kF1Arg>
 __device__ __forceinline__ int32_t decompress_block(const DecArgs& a, uint32_t cblk = 0, uint64_t cbase = 0) {
     __shared__ DecShared S;
+    const bool f1check = F1 == kF1Arg ? a.f1check != 0 : F1 == kF1On;
     const int lane = threadIdx.x;
     const uint32_t nseg = XP ? a.xsegs : 1u;   // XP: waves per block (one per segment)
     if (!CH && blockIdx.x >= a.nblocks * nseg) return 0;
@@ -2179,12 +2187,12 @@ __device__ __forceinline__ int32_t decompress_block(const DecArgs& a, uint32_t c
                 wave_run(c, S, lane, Run{(int32_t)tab_hi, (int32_t)cs.cll, (int32_t)cs.clit, 0, cs.cll ? (uint32_t)R_COMP : (uint32_t)R_NONE}, no_pat());
         }
         PROF(7);
-        if (a.f1check) {                                                    // 7
+        if (f1check) {                                                      // 7
             status = f1_table(c, S, lane, T.nseq);
             if (status) break;
         }
         if (kOutput && P.cut) {
-            status = cut_match(c, S, lane, (int32_t)(tab_hi + cs.cll), cs, a.f1check);
+            status = cut_match(c, S, lane, (int32_t)(tab_hi + cs.cll), cs, f1check);
             if (status) break;
         }
         advance(c, tab_hi, P, cs);
@@ -2228,7 +2236,14 @@ __device__ __forceinline__ int32_t decompress_block(const DecArgs& a, uint32_t c
     return status;
 }
 
-__global__ __launch_bounds__(64, 4) void lz4mi_decompress_kernel(DecArgs a) { (void)decompress_block<false>(a); }
+// the batch kernel, once per decode mode (DecArgs::f1check is not read): LZ4 spec ...
+__global__ __launch_bounds__(64, 4) void lz4mi_decompress_kernel(DecArgs a) {
+    (void)decompress_block<false, false, false, kF1Off>(a);
+}
+// ... and reference mode (LZ4MI_JS_EXACT; the redo launch of a small batch)
+__global__ __launch_bounds__(64, 4) void lz4mi_decompress_ref_kernel(DecArgs a) {
+    (void)decompress_block<false, false, false, kF1On>(a);
+}
 // small batches: a wave per segment of each block, sequences exported (lz4mi_expand.hip)
 __global__ __launch_bounds__(64, 4) void lz4mi_decompress_x_kernel(DecArgs a) { (void)decompress_block<true>(a); }
 // a linked window: every parsed block exported (no one-wave shortcuts)
@@ -2500,7 +2515,8 @@ extern "C" hipError_t lz4mi_launch_decompress(const Batch& b, int mode, int isol
                            nblocks, order);
         a.order = order;
     }
-    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_kernel, dim3(nblocks), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(mode == 2 ? lz4mi::lz4mi_decompress_ref_kernel : lz4mi::lz4mi_decompress_kernel, dim3(nblocks),
+                       dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -2591,7 +2607,7 @@ extern "C" hipError_t lz4mi_launch_decompress_small(const Batch& b, uint32_t x_i
     // batch kernel (LZ4MI_ERR_CROSS_BLOCK when batched); the launch is empty when there is none
     DecArgs r = dec_args(b, nblocks > 1 ? 1 : 0, 1);
     r.redo = L.redo.in<uint32_t>(xs);
-    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_kernel, dim3(nblocks), dim3(64), 0, stream, r);
+    hipLaunchKernelGGL(lz4mi::lz4mi_decompress_ref_kernel, dim3(nblocks), dim3(64), 0, stream, r);
     return hipGetLastError();
 }
 
